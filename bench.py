@@ -13,17 +13,27 @@ Metric (BASELINE.json): "Mkeys/s at 1/2/4/8 GPU (BSGS b125; addr b66); HBM GB/s 
   tertiary  : -m xpoint -f tests/63.pub -b 63 (configs[2]), same chunks, one key per point.
   --config 5: the primary on -m bsgs -f tests/130.txt -b 130 -k 512 (configs[4]) instead.
 
-Sustained measurement (throughput runs of >= 60 s after warm-up): the batch of a step
-(B bases, C chunks) is sized from the last warm-up step so that the K timed steps last --seconds
-(primary, default 60) and --seconds-secondary (default 20) per address-family leg; the line reports
-the rate of the first and the last quarter of the timed steps, each with its kernel time per launch,
-the board's gfx clock and socket power (amdsmi), and over the whole timed region the board's own
-counters (BoardSampler): mean socket power from the energy accumulator, the power cap, the share of
-the time spent at the package power limit (ppt_residency_frac, "power_capped") and points per joule.
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does what the headline needs and no more: it
+builds the tables, runs W warm-up steps and K timed steps of the primary leg and prints the line
+("value": Mkeys/s over the timed steps; "ms_per_step": the time of one of them).  A timed step is a
+fixed piece of work, STEP_TILES tiles of the engine's lanes (about 3.1 s), so --steps sets the length
+of the run and the same arguments walk the same bases in every run and on every build.
+--dump-outputs DIR then writes what the last timed step's kh_bsgs_scan calls returned as
+DIR/<name>.npy (dump_outputs: keys found if any, first-level candidates with their layer-2 masks, counters),
+for comparing two builds output for output.  --seconds S sizes the step from the last warm-up step
+instead, so that the K timed steps last S seconds whatever K is.
 
-Parity at full size: after each leg's timed loop (outside it), the same engine with the same tables
-scans the SURVEY.md 8c known-answer window of that workload and must find the reference's key
-("known_answer" per leg); bench.py exits 3 on a mismatch, after printing the line.
+--full is the sustained measurement (throughput runs of >= 60 s after warm-up): its
+primary leg runs with --seconds 60 unless told otherwise, and it adds everything else: the secondary
+and tertiary legs (a step of C chunks sized from the last
+warm-up step so that the timed steps last --seconds-secondary, default 20, per leg), the board's own
+view of each timed region (BoardSampler, amdsmi: gfx clock and socket power of the first and the last
+quarter of the timed steps, mean socket power from the energy accumulator, the power cap, the share
+of the time spent at the package power limit, ppt_residency_frac / "power_capped", and points per
+joule), the CPU baselines, and parity at full size: after each leg's timed loop (outside it), the same
+engine with the same tables scans the SURVEY.md 8c known-answer window of that workload and must
+find the reference's key ("known_answer" per leg); bench.py --full exits 3 on a mismatch, after
+printing the line.  Without --full those fields of the line are null.
 
 Ranks split the keyspace (weak scaling, no collective on the data path): rank r walks its own
 contiguous region starting at r * span units (rank_origin), so consecutive steps continue the same
@@ -55,7 +65,7 @@ The HBM side is reported too ("hbm"): algorithmic bytes (BSGS: 64 B per giant po
 of the blocked layer 1; the reference layout's is 128 B) / launch time against 8 TB/s,
 and traffic = HBM bytes per launch from the PMC counters with the guide's gfx950 corrections
 (tools/pmc_summary.py), or null.
-cpu_baseline: rank 0 at N=1 only, on every leg the reference binary built from its own sources with
+cpu_baseline (--full): rank 0 at N=1 only, on every leg the reference binary built from its own sources with
 its own optimisation flags (oracle/_ref/keyhunt_fast, oracle/Makefile.ref; kind "reference"), run for
 --cpu-seconds-primary (BSGS) / --cpu-seconds (rmd160, xpoint), 60 s each, of its own stats clock on the
 job's CPU share (cpu_threads: "value", "threads"), then for --cpu-seconds-per-core (30 s) with -t 1
@@ -64,7 +74,7 @@ per core come from lscpu.  BSGS skips the reference's
 baby-step build: the engine writes the -S table files in the reference's format (kh_bsgs_save,
 byte-identical) and the reference reads them (-S -6).
 
-The line ends with "legs": one compact object per leg (value, unit, known-answer match, roofline frac,
+The line ends with "legs": one compact object per leg that ran (value, unit, known-answer match, roofline frac,
 the CPU baseline's value and sample seconds), so the three legs' numbers sit in the last bytes of the
 line, which a runner that keeps only the tail of stdout still holds.
 """
@@ -245,6 +255,9 @@ class Walks:
 # wave slot, which gets the same (kh_kernels.h KH_LANES_HB, profiles/r04a_geom_ab.json)
 WALKS_BSGS = 1
 WALKS_ADDRESS = 1
+# a timed BSGS step: this many tiles of the engine's lanes (2^33 giant points a tile), about 3.1 s on one
+# MI355X -- the step the sustained runs recorded in profiles/r06*_bench.json were sized to
+STEP_TILES = 15
 
 
 def batch_for(seconds: float, steps: int, unit_s: float, quantum: int, floor: int) -> int:
@@ -573,13 +586,25 @@ def bsgs_leg(D: Dist, W: Walks, args, clock):
     B0 = args.bases or C["bases"]
     assert B0 % S == 0, "--bases must be a multiple of --walks"
     walked = 0
+    last_step = None
 
-    def run(nb):
-        # nb bases per step in all, nb / S per context, each in its own part of the rank's region
-        nonlocal walked
+    def run(nb, keep=False):
+        # nb bases per step in all, nb / S per context, each in its own part of the rank's region;
+        # keep (--dump-outputs, last timed step): hold what the step's calls returned (last_step)
+        nonlocal walked, last_step
         per = nb // S
         assert walked + per <= RANK_SPAN_BASES // S, "rank region exhausted"
+        if keep:
+            before = W.each(lambda i, e: (e.bsgs_log_candidates(True), e.bsgs_refine_stats())[1])
         found = W.each(lambda i, e: e.bsgs_scan(walk_origin(origin, i, S, RANK_SPAN_BASES, two_n) + walked * two_n, per))
+        if keep:
+            after = W.each(lambda i, e: e.bsgs_refine_stats())
+            cands = W.each(lambda i, e: [(i * per + b, a, m) for b, a, m in e.bsgs_logged_candidates()])
+            W.each(lambda i, e: e.bsgs_log_candidates(False))
+            last_step = {"first_base": walked, "bases": nb, "giant_points": nb * info.cycles * 1024,
+                         "found": sum(found, []), "candidates": sum(cands, []),
+                         "first_level": sum(a[0] - b[0] for a, b in zip(after, before)),
+                         "layer2_hits": sum(a[1] - b[1] for a, b in zip(after, before))}
         walked += per
         assert not any(found)  # puzzle 125's (130's) key lies far from the start of the range
 
@@ -588,28 +613,41 @@ def bsgs_leg(D: Dist, W: Walks, args, clock):
     # §2 "Placement"), so it happens here and not in the timed region; 2^24 groups: parts of 2^34 points
     gpb = max(1, info.cycles * 1024 // 4096)
     Bw = max(B0, -(-(8 << 21) // gpb) * S) if args.warmup else B0
+    # whole tiles of the engine's 2^21 lanes (2^18 bases of 8 groups at k = 128): consecutive steps
+    # then continue their lanes, and no ragged last round walks unprobed points
+    lanes = int(os.environ.get("KH_BSGS_LANES", 1 << 21))
+    tile = lanes // gpb * S
+    if args.seconds is None:
+        # the step is a fixed piece of work (STEP_TILES tiles, or --bases), so the same arguments
+        # walk the same bases in every run and on every build; a warm-up step is no smaller than a
+        # timed one, so (warm-up + timed steps) x ms_per_step never exceeds the run
+        B = B0 if args.bases else STEP_TILES * tile
+        Bw = max(Bw, B) if args.warmup else Bw
     last = 0.0
     for s in range(args.warmup):
         t = time.perf_counter()
         run(Bw)
         last = time.perf_counter() - t
-    B = int(D.max(batch_for(args.seconds, args.steps, last / Bw, B0, B0) if args.warmup else B0))
-    # whole tiles of the engine's 2^21 lanes (2^18 bases of 8 groups at k = 128): consecutive steps
-    # then continue their lanes, and no ragged last round walks unprobed points
-    lanes = int(os.environ.get("KH_BSGS_LANES", 1 << 21))
-    tile = lanes // max(1, info.cycles * 1024 // 4096) * S
-    if not args.bases and B >= tile:
-        B = max(tile, (B + tile // 2) // tile * tile)
+    if args.seconds is not None:
+        B = int(D.max(batch_for(args.seconds, args.steps, last / Bw, B0, B0) if args.warmup else B0))
+        if not args.bases and B >= tile:
+            B = max(tile, (B + tile // 2) // tile * tile)
     progress(f"BSGS warm-up done; timing {args.steps} steps of {B} bases")
-    T, t0, t1, recs, board = timed(D, W, args.steps, lambda s: run(B), B, K.engine.TIME_BSGS, clock)
-    progress(f"BSGS timed region {T:.1f} s; known-answer window next")
+    keep = bool(args.dump_outputs)
+    T, t0, t1, recs, board = timed(D, W, args.steps, lambda s: run(B, keep and s == args.steps - 1), B,
+                                   K.engine.TIME_BSGS, clock)
+    progress(f"BSGS timed region {T:.1f} s")
     lanes_pick, rate_hi, rate_lo = W.engs[0].bsgs_geometry()
     cal_done, cal_rates = W.engs[0].bsgs_placement()
     la, ms, pts = W.kernel_time(K.engine.TIME_BSGS)
     my_pts_s = args.steps * B * info.cycles * 1024 / (recs[-1][0] - t0)
-    # known answer (outside the timed region, same engine and tables): SURVEY.md 8c
-    ka_lo, ka_hi, ka_key = C["ka"]
-    ka_found = W.engs[0].bsgs_scan(ka_lo, (ka_hi - ka_lo) // two_n)
+    # known answer (--full; outside the timed region, same engine and tables): SURVEY.md 8c
+    known = None
+    if args.full:
+        ka_lo, ka_hi, ka_key = C["ka"]
+        ka_found = W.engs[0].bsgs_scan(ka_lo, (ka_hi - ka_lo) // two_n)
+        known = {"window": f"{ka_lo:x}:{ka_hi:x}", "expected": f"{ka_key:x}",
+                 "found": [f"{k:x}" for _, k in ka_found], "match": [k for _, k in ka_found] == [ka_key]}
     keys = D.world * args.steps * B * two_n
     pts_launch = pts / la
     ms_launch = chip_ms_per_launch(S, ms, la, t1 - t0)
@@ -638,8 +676,8 @@ def bsgs_leg(D: Dist, W: Walks, args, clock):
         "info": info,
         "roofline": roof,
         "sustained": quarters(t0, recs, B, two_n, clock, board, my_pts_s),
-        "known_answer": {"window": f"{ka_lo:x}:{ka_hi:x}", "expected": f"{ka_key:x}",
-                         "found": [f"{k:x}" for _, k in ka_found], "match": [k for _, k in ka_found] == [ka_key]},
+        "known_answer": known,
+        "last_step": last_step,
     }
 
 
@@ -969,11 +1007,47 @@ def legs_summary(line: dict) -> dict:
             continue
         cb = leg.get("cpu_baseline") or {}
         th = cb.get("threads") or {}
-        out[name] = {"value": leg["value"], "unit": leg["unit"], "known_answer_match": leg["known_answer"]["match"],
+        out[name] = {"value": leg["value"], "unit": leg["unit"],
+                     "known_answer_match": (leg.get("known_answer") or {}).get("match"),
                      "frac": (leg.get("roofline") or {}).get("frac"),
                      "cpu_baseline": {"value": cb.get("value"), "threads": th.get("threads"), "seconds": th.get("seconds"),
                                       "per_core_seconds": (cb.get("per_core") or {}).get("seconds")} if cb else None}
     return out
+
+
+DUMP_MAX_ROWS = 1 << 20  # candidate rows kept by --dump-outputs (24 MB of float64): beyond that a seeded sample
+
+
+def dump_outputs(directory: str, rank: int, step: dict) -> dict:
+    """--dump-outputs: what the kh_bsgs_scan calls of the last timed BSGS step gave their caller, as
+    DIR/<name>.npy in float64 (rank r > 0: <name>_rank<r>.npy); returns {name: shape}.  An array
+    without rows is not written (and a file of its name from an earlier run is removed): counters says
+    how many rows there were.
+      found       a row per key found: target index, then the key in eight 32-bit limbs, most
+                  significant first (none on the puzzle workloads: their keys lie far from the start)
+      candidates  a row per first-level candidate of the step (kh_bsgs_get_candidates): base ordinal
+                  within the step, giant-step index, layer-2 mask of the second check; sorted, and
+                  beyond DUMP_MAX_ROWS a fixed sample (numpy default_rng(0)) of the sorted rows
+      counters    first base of the step counted from the walk's origin, bases, giant points,
+                  first-level candidates, layer-2 hits of their second checks, keys found"""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    found = np.array([[t] + [(k >> (32 * (7 - j))) & 0xFFFFFFFF for j in range(8)] for t, k in step["found"]],
+                     dtype=np.float64).reshape(-1, 9)
+    cands = np.array(sorted(step["candidates"]), dtype=np.float64).reshape(-1, 3)
+    if len(cands) > DUMP_MAX_ROWS:
+        cands = cands[np.sort(np.random.default_rng(0).choice(len(cands), DUMP_MAX_ROWS, replace=False))]
+    counters = np.array([step["first_base"], step["bases"], step["giant_points"], step["first_level"],
+                         step["layer2_hits"], len(found)], dtype=np.float64)
+    shapes = {}
+    for name, a in (("found", found), ("candidates", cands), ("counters", counters)):
+        path = os.path.join(directory, name + (f"_rank{rank}" if rank else "") + ".npy")
+        if len(a):
+            np.save(path, a)
+            shapes[name] = list(a.shape)
+        elif os.path.exists(path):
+            os.remove(path)
+    return shapes
 
 
 def main():
@@ -996,10 +1070,18 @@ def main():
                     help="BSGS workload: 4 = b125 k128 (the metric's), 5 = b130 k512")
     ap.add_argument("--bases", type=int, default=0,
                     help="BSGS bases per warm-up step per GPU, and the quantum of the timed steps' batch (0: per config)")
-    ap.add_argument("--seconds", type=float, default=60.0,
-                    help="size the BSGS batch so that the timed steps last this long (0: --bases per step)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline BSGS leg: its known-answer window, the rmd160 and xpoint legs, the "
+                         "board's clock / power / power-limit counters and the CPU baselines of the reference")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed BSGS step returned as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--seconds", type=float, default=None,
+                    help="size the BSGS batch from the warm-up so that the timed steps last this long (0: --bases per "
+                         "step); default: a fixed step of STEP_TILES lane tiles, the same bases in every run, and 60 "
+                         "with --full (unless --dump-outputs asks for the fixed step)")
     ap.add_argument("--seconds-secondary", type=float, default=20.0,
-                    help="the same for each address-family leg (0: one 2^32-key chunk per step)")
+                    help="--full: size each address-family leg's batch so that its timed steps last this long "
+                         "(0: one 2^32-key chunk per step)")
     ap.add_argument("--steps-rmd", type=int, default=None)
     ap.add_argument("--warmup-rmd", type=int, default=None)
     ap.add_argument("--cpu-seconds", type=float, default=60.0,
@@ -1024,15 +1106,21 @@ def main():
     args = ap.parse_args()
     args.steps_rmd = args.steps if args.steps_rmd is None else args.steps_rmd
     args.warmup_rmd = args.warmup if args.warmup_rmd is None else args.warmup_rmd
+    if args.full and args.seconds is None and not args.dump_outputs:
+        args.seconds = 60.0  # the sustained window, whatever --steps is
+    if args.dump_outputs and args.seconds is not None:
+        sys.exit("bench.py: --dump-outputs needs the fixed step (--seconds sizes the step from this run's warm-up, "
+                 "so two runs would not walk the same bases)")
+    legs = args.full and not args.no_secondary
 
     import keyhunt_amd as K
     D = Dist()
     if args.gpus != D.world:
         sys.exit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={D.world}: launch one rank per GPU")
     dev = device_plan(D.world, D.local, D.local_world, K.device_count(), args.rehearse)
-    W = Walks(K, dev, max(args.walks, 1 if args.no_secondary else args.walks_secondary))
+    W = Walks(K, dev, max(args.walks, args.walks_secondary if legs else 1))
     bdf = pci_bus_id(dev)
-    clock = BoardSampler(bdf).start()
+    clock = BoardSampler(bdf).start() if args.full else None
     if args.cpu_only:  # the reference's rates alone (profiles/r04*_cpu_baseline_*.json)
         C = BSGS_CONFIGS[args.config]
         W.engs[0].bsgs_setup(1 << 44, C["k"], layer1=args.layer1)
@@ -1046,22 +1134,29 @@ def main():
         json_out.flush()
         return
     prim = bsgs_leg(D, W.head(args.walks), args, clock)
-    Wa = W.head(args.walks_secondary)
-    sec = None if args.no_secondary else rmd160_leg(D, Wa, args, clock)
-    ter = None if args.no_secondary else xpoint_leg(D, Wa, args, clock)
-    clock.stop()
+    dumped = dump_outputs(args.dump_outputs, D.rank, prim["last_step"]) if args.dump_outputs else None
+    # everything below that is not the headline's own (--full): the address-family legs, the CPU baselines
+    sec = ter = None
+    if legs:
+        Wa = W.head(args.walks_secondary)
+        sec = rmd160_leg(D, Wa, args, clock)
+        ter = xpoint_leg(D, Wa, args, clock)
+    if clock:
+        clock.stop()
     cpu_b = cpu_r = cpu_x = None
-    if D.rank == 0 and D.world == 1 and not args.no_cpu_baseline and not args.cpu_only:
+    if args.full and D.rank == 0 and D.world == 1 and not args.no_cpu_baseline:
         pc = args.cpu_seconds_per_core
         cpu_b = cpu_baseline_bsgs(W.engs[0], BSGS_CONFIGS[args.config], args.cpu_seconds_primary, pc)
-        if not args.no_secondary:
+        if legs:
             cpu_r = cpu_baseline_rmd160(args.cpu_seconds, pc)
             cpu_x = cpu_baseline_xpoint(args.cpu_seconds, pc)
     W.close()
     ranks = D.gather({"rank": D.rank, "host": os.uname().nodename, "device": dev, "pci_bus_id": bdf,
                       "giant_points_per_s": prim["rank_giant_points_per_s"]})
-    kas = [prim["known_answer"]] + [x["known_answer"] for x in (sec, ter) if x]
-    ka_ok = D.sum(float(all(k["match"] for k in kas))) == D.world
+    ka_ok = None
+    if args.full:
+        kas = [prim["known_answer"]] + [x["known_answer"] for x in (sec, ter) if x]
+        ka_ok = D.sum(float(all(k["match"] for k in kas))) == D.world
     D.barrier()
     if D.rank == 0:
         info = prim["info"]
@@ -1090,8 +1185,11 @@ def main():
             "sustained": prim["sustained"],
             "roofline": prim["roofline"],
             "random_access": prim["random_access"],
-            "board_sampler": dict(clock.info(), source="amdsmi gpu_metrics / energy counter of the rank-0 device"),
+            "board_sampler": (dict(clock.info(), source="amdsmi gpu_metrics / energy counter of the rank-0 device")
+                              if clock else None),
             "cpu_baseline": cpu_b,
+            "full": args.full,
+            "dumped_outputs": dumped,
         }
         for key, leg, wl in (("secondary", sec, "-m rmd160 -f tests/66.rmd -b 66 -l compress"),
                              ("tertiary", ter, "-m xpoint -f tests/63.pub -b 63")):
@@ -1107,7 +1205,7 @@ def main():
         json_out.write(json.dumps(line) + "\n")
         json_out.flush()
     D.close()
-    if not ka_ok:
+    if args.full and not ka_ok:
         sys.exit(3)
 
 

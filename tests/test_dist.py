@@ -106,6 +106,44 @@ def test_batch_for_sizes_the_sustained_window(seconds, steps, unit_s, quantum, e
         assert b * steps * unit_s >= seconds * 0.999
 
 
+def test_dump_outputs_writes_sorted_float64_arrays(tmp_path):
+    """--dump-outputs: the last step's keys, candidates and counters as float64 .npy files; the
+    candidates sorted (the engine appends them in the order its waves found them), a found key in
+    eight 32-bit limbs, and beyond DUMP_MAX_ROWS candidates the same sample of them every time."""
+    import numpy as np
+    import bench
+    key = 0x1c533b6bb7f0804e09960225e44877ac
+    step = {"first_base": 3, "bases": 8, "giant_points": 8 << 15, "found": [(0, key)],
+            "candidates": [(5, 7, 0), (1, 30000, 2), (1, 12, 1)], "first_level": 3, "layer2_hits": 2}
+    shapes = bench.dump_outputs(str(tmp_path / "d"), 0, step)
+    assert shapes == {"found": [1, 9], "candidates": [3, 3], "counters": [6]}
+    got = {n: np.load(tmp_path / "d" / f"{n}.npy") for n in shapes}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["candidates"].tolist() == [[1, 12, 1], [1, 30000, 2], [5, 7, 0]]
+    assert got["counters"].tolist() == [3, 8, 8 << 15, 3, 2, 1]
+    assert got["found"][0, 0] == 0 and sum(int(v) << (32 * (7 - j)) for j, v in enumerate(got["found"][0, 1:])) == key
+    # no key found, rank 1, more candidates than the cap: no found file (an earlier one is removed,
+    # the counters say 0 keys), a repeatable sorted sample
+    many = dict(step, found=[], candidates=[(b, 1, 0) for b in range(bench.DUMP_MAX_ROWS + 100)])
+    (tmp_path / "a").mkdir()
+    (tmp_path / "a" / "found_rank1.npy").write_bytes(b"stale")
+    a = bench.dump_outputs(str(tmp_path / "a"), 1, many)
+    bench.dump_outputs(str(tmp_path / "b"), 1, many)
+    assert a == {"candidates": [bench.DUMP_MAX_ROWS, 3], "counters": [6]}
+    assert sorted(os.listdir(tmp_path / "a")) == ["candidates_rank1.npy", "counters_rank1.npy"]
+    assert np.load(tmp_path / "a" / "counters_rank1.npy")[5] == 0
+    ca, cb = np.load(tmp_path / "a" / "candidates_rank1.npy"), np.load(tmp_path / "b" / "candidates_rank1.npy")
+    assert (ca == cb).all() and (np.diff(ca[:, 0]) > 0).all()
+
+
+def test_dump_outputs_refuses_a_step_sized_from_the_warmup():
+    """--seconds sizes the step from this run's warm-up, so two runs would not walk the same bases:
+    refused with --dump-outputs before anything touches the GPU."""
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--seconds", "5", "--dump-outputs", "x"],
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode != 0 and "--dump-outputs needs the fixed step" in p.stderr
+
+
 def test_more_ranks_than_gpus_is_refused_unless_rehearsal():
     import bench
     assert [bench.device_plan(8, r, 8, 8, False) for r in range(8)] == list(range(8))

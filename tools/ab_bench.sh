@@ -6,7 +6,7 @@ set -o pipefail
 O=gpurun_out/ab; mkdir -p $O
 for v in "$@"; do
   if [ $v = main ]; then L=keyhunt_amd/lib/libkh_gpu.so; else L=variants/$v/libkh_gpu.so; fi
-  KH_LIB=$L timeout -k 10 300 python bench.py --no-cpu-baseline > $O/$v.json 2> $O/$v.err || { echo "bench $v rc=$?"; tail -20 $O/$v.err; exit 1; }
+  KH_LIB=$L timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/$v.json 2> $O/$v.err || { echo "bench $v rc=$?"; tail -20 $O/$v.err; exit 1; }
 done
 python - "$@" <<'P'
 import json, sys

@@ -3,7 +3,7 @@
 # judged on >= 3 A-B pairs, with their spread recorded):
 #   tools/ab_interleave.sh PAIRS A B [bench.py args ...]
 # A / B: "main" (keyhunt_amd/lib) or a variant of tools/build_variants.sh (variants/NAME/libkh_gpu.so).
-# Runs A B A B ... (PAIRS pairs) of `bench.py --no-cpu-baseline` with short windows (override with
+# Runs A B A B ... (PAIRS pairs) of `bench.py --full --no-cpu-baseline` with short windows (override with
 # bench args), then writes gpurun_out/ab/interleave_A_B.json: every run's BSGS wall / kernel rate,
 # rmd160 and xpoint kernel rates, board clock and power, and per build the mean and min..max.
 set -o pipefail
@@ -14,7 +14,7 @@ lib() { if [ $1 = main ]; then echo keyhunt_amd/lib/libkh_gpu.so; else echo vari
 for i in $(seq 1 $PAIRS); do
   for v in $A $B; do
     echo "[ab] pair $i: $v" >&2
-    KH_LIB=$(lib $v) timeout -k 10 240 python bench.py --no-cpu-baseline $ARGS > $O/il_${v}_$i.json 2> $O/il_${v}_$i.err \
+    KH_LIB=$(lib $v) timeout -k 10 240 python bench.py --full --no-cpu-baseline $ARGS > $O/il_${v}_$i.json 2> $O/il_${v}_$i.err \
       || { echo "bench $v pair $i rc=$?"; tail -20 $O/il_${v}_$i.err; exit 1; }
   done
 done

@@ -7,7 +7,7 @@ O=gpurun_out/$TAG; mkdir -p $O
 for v in "$@"; do
   if [ $v = main ]; then L=keyhunt_amd/lib/libkh_gpu.so; else L=variants/$v/libkh_gpu.so; fi
   rc=0
-  KH_LIB=$L timeout -k 10 200 python bench.py --no-cpu-baseline --no-secondary --seconds 15 > $O/$v.json 2> $O/$v.err || rc=$?
+  KH_LIB=$L timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-secondary --seconds 15 > $O/$v.json 2> $O/$v.err || rc=$?
   if [ $rc -ne 0 ] && [ $rc -ne 3 ]; then echo "bench $v rc=$rc"; tail -20 $O/$v.err; exit 1; fi
   python3 -c "
 import json;d=json.loads(open('$O/$v.json').read().strip().splitlines()[-1]); s=d['sustained']

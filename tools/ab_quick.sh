@@ -16,7 +16,7 @@ i=0
 for v in "$@"; do
   i=$((i + 1))
   if [ $v = main ]; then L=keyhunt_amd/lib/libkh_gpu.so; else L=variants/$v/libkh_gpu.so; fi
-  KH_LIB=$L timeout -k 10 300 python bench.py --no-cpu-baseline --seconds 12 --seconds-secondary 6 > $O/ab${i}_$v.json 2> $O/ab${i}_$v.err \
+  KH_LIB=$L timeout -k 10 300 python bench.py --full --no-cpu-baseline --seconds 12 --seconds-secondary 6 > $O/ab${i}_$v.json 2> $O/ab${i}_$v.err \
     || { echo "ab $v rc=$?"; tail -20 $O/ab${i}_$v.err; exit 1; }
   python3 -c "
 import json;d=json.load(open('$O/ab${i}_$v.json'))

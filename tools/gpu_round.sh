@@ -18,13 +18,13 @@ if has tests; then
   [ $TESTS_RC -gt 1 ] && { echo "tests rc=$TESTS_RC"; exit 1; }
 fi
 if has bench; then
-  timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || { echo "bench rc=$?"; tail -20 $O/bench.err; exit 1; }
+  timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || { echo "bench rc=$?"; tail -20 $O/bench.err; exit 1; }
   cat $O/bench.json
 fi
 cd /tmp && export TMPDIR=/tmp
 if has prof; then
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- \
-    python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/prof.json 2> $O/prof.err \
+    python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $O/prof.json 2> $O/prof.err \
     || { echo "prof rc=$?"; tail -20 $O/prof.err; exit 1; }
   echo "prof ok"
 fi
@@ -48,7 +48,7 @@ if has ubench; then
   cat $O/ubench_cost.txt
 fi
 if has config5; then
-  timeout -k 10 600 python $R/bench.py --config 5 > $O/bench_c5.json 2> $O/bench_c5.err || { echo "bench c5 rc=$?"; tail -20 $O/bench_c5.err; exit 1; }
+  timeout -k 10 600 python $R/bench.py --full --config 5 > $O/bench_c5.json 2> $O/bench_c5.err || { echo "bench c5 rc=$?"; tail -20 $O/bench_c5.err; exit 1; }
   cat $O/bench_c5.json
 fi
 exit $TESTS_RC

@@ -7,7 +7,7 @@ set -o pipefail
 R=$(pwd); O=$R/gpurun_out/${1:-r03b}; mkdir -p $O
 timeout -k 10 120 tools/ubench_cost > $O/ubench_cost.txt 2>&1 || { echo "ubench rc=$?"; cat $O/ubench_cost.txt; exit 1; }
 cat $O/ubench_cost.txt
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || { echo "bench rc=$?"; tail -20 $O/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || { echo "bench rc=$?"; tail -20 $O/bench.err; exit 1; }
 cat $O/bench.json
 for v in main xnops main xnops; do
   if [ $v = main ]; then L=keyhunt_amd/lib/libkh_gpu.so; else L=variants/$v/libkh_gpu.so; fi

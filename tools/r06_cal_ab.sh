@@ -23,7 +23,7 @@ for i in $(seq 1 $P); do
       nocalb) E="KH_BSGS_CALIBRATE=0 KH_BURN_MS=1000";;
       lanesb) E="KH_BURN_MS=1000";;
     esac
-    env $E timeout -k 10 300 python bench.py --no-secondary --no-cpu-baseline --seconds 30 --steps 5 --warmup 2 \
+    env $E timeout -k 10 300 python bench.py --full --no-secondary --no-cpu-baseline --seconds 30 --steps 5 --warmup 2 \
       > $O/${v}_$i.json 2> $O/${v}_$i.err || { echo "$v $i rc=$?"; tail -5 $O/${v}_$i.err; exit 1; }
     python3 -c "import json; d=json.loads(open('$O/${v}_$i.json').read().strip().splitlines()[-1]); c=d['config']['placement_calibration']; print('$v', $i, round(d['giant_points_per_s']/1e9,3), [round(x/1e9,2) for x in (c['pad_giant_points_per_s_kept'], c['pad_other'], c['layer1_giant_points_per_s_kept'], c['layer1_other'])], round(d['sustained']['board'].get('board_gfxclk_mhz') or 0))"
   done
