@@ -337,18 +337,11 @@ struct kh_ctx {
   uint32_t lanes_pick = 0, lanes_force = 0;
   uint32_t lanes_used = 0;  // lanes the last large-group BSGS call walked (the calibration checks it)
   bool bsgs_calibrated = false;
-  // giant points/s of the placement calibration's candidates (stage 0: the pad, 1: layer 1):
-  // [2s] the one kept, [2s + 1] the best other one; cal_stage: stages decided so far
-  double cal_rate[4] = {0, 0, 0, 0};
-  int cal_stage = 0;
-  uint64_t cal_moved_bases = 0;  // bases the last KH_CAL_MOVE stage walked
-  uint32_t cal_deferred = 0;      // eligible calls walked uncalibrated (KH_CAL_DEFER)
-  bool burned = false;            // KH_BURN_MS ran before this context's first large BSGS call
-  double burn_ms = 0;
+  // giant points/s of the calibration's two candidates: [0] the one kept, [1] the other
+  double cal_rate[2] = {0, 0};
   uint32_t groups_per_launch = 0;
   uint32_t lanes_alloc = 0;
   int scratch_h = 0;  // inversion-pad entries per lane in d_scratch
-  uint32_t pad_skew = 0;  // lanes of gap after each pad row (KH_PAD_SKEW, read when the pad is allocated)
   // continuous BSGS lanes kept across kh_bsgs_scan calls: valid while the lane centres sit at the
   // first group of the call that would start at cont_next (same target, lanes and group size)
   bool cont_valid = false;
@@ -360,8 +353,6 @@ struct kh_ctx {
   uint32_t *d_q = nullptr;  // the current BSGS target {x[8], y[8]}
   uint32_t *d_cx = nullptr, *d_cy = nullptr, *d_scalars = nullptr;
   uint4 *d_scratch = nullptr;
-  void *d_scratch_base = nullptr;  // the pad's allocation (d_scratch sits KH_PAD_OFFSET bytes into it)
-  uint64_t pad_offset = 0;
   std::vector<uint32_t> h_scalars;
 
   // walk delta tables: key -> device table ((H+1) x 16 words)
@@ -452,7 +443,7 @@ kh_ctx::~kh_ctx() {
   (void)hipFree(d_cx);
   (void)hipFree(d_cy);
   (void)hipFree(d_scalars);
-  (void)hipFree(d_scratch_base);
+  (void)hipFree(d_scratch);
   (void)hipFree(d_q);
   for (auto &t : tables) (void)hipFree(t.second);
   (void)hipFree(d_hit_count);
@@ -487,70 +478,23 @@ namespace {
 
 // lane centres for L lanes and an inversion pad of H rows per lane (walk_pad_rows: half the group for
 // the sparse-pad walks)
-// Device memory for the randomly probed layer-1 filter (which = 1) and the giant walk's inversion pad
-// (which = 2).  KH_CONTIG=<mask> asks for physically contiguous memory (hipDeviceMallocContiguous)
-// for an A/B; the default is an ordinary allocation: contiguous layer 1 + pad walked 35.7 / 34.5 /
-// 36.0 G giant points/s against 40.0 / 39.7 / 37.4 ordinary, interleaved in the bench's BSGS leg
-// (profiles/r05an_bench_contig_ab.json)
-hipError_t dev_alloc(void **p, size_t bytes, int which) {
-  static const int mask = [] {
-    const char *e = getenv("KH_CONTIG");
-    return e ? atoi(e) : 0;
-  }();
-  static const bool log = getenv("KH_DEBUG_ALLOC") != nullptr;  // diagnostics only: stderr
-  if (mask & which) {
-    if (hipExtMallocWithFlags(p, bytes, hipDeviceMallocContiguous) == hipSuccess) {
-      if (log) fprintf(stderr, "[kh] %zu bytes (kind %d): contiguous\n", bytes, which);
-      return hipSuccess;
-    }
-    (void)hipGetLastError();
-    *p = nullptr;
-    if (log) fprintf(stderr, "[kh] %zu bytes (kind %d): contiguous refused\n", bytes, which);
-  }
-  return hipMalloc(p, bytes);
-}
-
-// KH_PAD_SKEW=<lanes>: a gap of that many lane entries after every pad row, so rows sit L + skew
-// entries apart instead of a power of two (A/B knob; 0 by default)
-static uint32_t env_pad_skew() {
-  const char *e = getenv("KH_PAD_SKEW");
-  return e ? (uint32_t)strtoul(e, nullptr, 0) : 0u;
-}
-
-// KH_PAD_SWZ=1: rotate each pad row's columns by workgroup (walk_args::pad_swz), when the lanes allow
-static uint32_t pad_swizzle(uint32_t L) {
-  const char *e = getenv("KH_PAD_SWZ");  // read per launch: A/B tools switch it inside one process
-  return e && atoi(e) && L % 2048 == 0 ? 1u : 0u;
-}
-
-// KH_PAD_OFFSET=<bytes>: the pad starts that far (rounded down to 256 B) into its allocation (A/B knob)
-static uint64_t env_pad_offset() {
-  const char *e = getenv("KH_PAD_OFFSET");
-  return e ? strtoull(e, nullptr, 0) & ~255ull : 0ull;
-}
-
 int ensure_lanes(kh_ctx *c, uint32_t L, int H = KH_WALK_H) {
-  if (L <= c->lanes_alloc && H <= c->scratch_h && c->pad_skew == env_pad_skew() && c->pad_offset == env_pad_offset())
-    return KH_OK;
+  if (L <= c->lanes_alloc && H <= c->scratch_h) return KH_OK;
   L = std::max(L, c->lanes_alloc);
   H = std::max(H, c->scratch_h);
   c->cont_valid = false;
   (void)hipFree(c->d_cx);
   (void)hipFree(c->d_cy);
   (void)hipFree(c->d_scalars);
-  (void)hipFree(c->d_scratch_base);
+  (void)hipFree(c->d_scratch);
   c->d_cx = c->d_cy = c->d_scalars = nullptr;
   c->d_scratch = nullptr;
-  c->d_scratch_base = nullptr;
   c->lanes_alloc = 0;
   c->scratch_h = 0;
-  c->pad_skew = env_pad_skew();
   HIPCHK(c, hipMalloc(&c->d_cx, (size_t)L * 32));
   HIPCHK(c, hipMalloc(&c->d_cy, (size_t)L * 32));
   HIPCHK(c, hipMalloc(&c->d_scalars, (size_t)L * 32));
-  c->pad_offset = env_pad_offset();
-  HIPCHK(c, dev_alloc(&c->d_scratch_base, ((size_t)L + c->pad_skew) * H * 32 + c->pad_offset, 2));
-  c->d_scratch = reinterpret_cast<uint4 *>(static_cast<uint8_t *>(c->d_scratch_base) + c->pad_offset);
+  HIPCHK(c, hipMalloc(&c->d_scratch, (size_t)L * H * 32));
   c->lanes_alloc = L;
   c->scratch_h = H;
   return KH_OK;
@@ -850,10 +794,9 @@ int kh_release_walk(kh_ctx *ctx) {
   (void)hipFree(ctx->d_cx);
   (void)hipFree(ctx->d_cy);
   (void)hipFree(ctx->d_scalars);
-  (void)hipFree(ctx->d_scratch_base);
+  (void)hipFree(ctx->d_scratch);
   ctx->d_cx = ctx->d_cy = ctx->d_scalars = nullptr;
   ctx->d_scratch = nullptr;
-  ctx->d_scratch_base = nullptr;
   ctx->lanes_alloc = 0;
   ctx->scratch_h = 0;
   ctx->cont_valid = false;
@@ -862,7 +805,7 @@ int kh_release_walk(kh_ctx *ctx) {
 
 int kh_bsgs_geometry(kh_ctx *ctx, uint32_t *lanes, double rates[2]) {
   if (!ctx) return KH_E_ARG;
-  if (lanes) *lanes = ctx->cal_stage >= 1 ? ctx->lanes_pick : 0;
+  if (lanes) *lanes = ctx->lanes_pick;
   if (rates) {
     rates[0] = ctx->cal_rate[0];
     rates[1] = ctx->cal_rate[1];
@@ -872,93 +815,10 @@ int kh_bsgs_geometry(kh_ctx *ctx, uint32_t *lanes, double rates[2]) {
 
 int kh_bsgs_placement(kh_ctx *ctx, double rates[4]) {
   if (!ctx || !rates) return KH_E_ARG;
-  for (int k = 0; k < 4; k++) rates[k] = ctx->cal_rate[k];
+  rates[0] = ctx->cal_rate[0];
+  rates[1] = ctx->cal_rate[1];
+  rates[2] = rates[3] = 0.0;  // no layer-1 stage
   return ctx->bsgs_calibrated ? 1 : 0;
-}
-
-// a fresh allocation for one device buffer: the new one is taken while the old is held, the contents
-// copied, then the old one freed
-static int move_buffer(kh_ctx *ctx, void **p, size_t bytes, int which) {
-  if (!*p) return KH_OK;
-  void *nb = nullptr;
-  HIPCHK(ctx, which ? dev_alloc(&nb, bytes, which) : hipMalloc(&nb, bytes));
-  HIPCHK(ctx, hipMemcpy(nb, *p, bytes, hipMemcpyDeviceToDevice));
-  (void)hipFree(*p);
-  *p = nb;
-  return KH_OK;
-}
-
-int kh_debug_replace(kh_ctx *ctx, uint32_t which) {
-  if (!ctx) return KH_E_ARG;
-  (void)hipSetDevice(ctx->device);
-  HIPCHK(ctx, hipDeviceSynchronize());
-  int r = KH_OK;
-  if ((which & 1) && ctx->d_bl[0])
-    r = move_buffer(ctx, reinterpret_cast<void **>(&ctx->d_bl[0]), 256 * ctx->bd[0].stride + 4, 1);
-  if (!r && (which & 2) && ctx->d_scratch_base) {  // the pad (no contents to keep)
-    const size_t bytes = ((size_t)ctx->lanes_alloc + ctx->pad_skew) * ctx->scratch_h * 32 + ctx->pad_offset;
-    void *nb = nullptr;
-    HIPCHK(ctx, dev_alloc(&nb, bytes, 2));
-    (void)hipFree(ctx->d_scratch_base);
-    ctx->d_scratch_base = nb;
-    ctx->d_scratch = reinterpret_cast<uint4 *>(static_cast<uint8_t *>(nb) + ctx->pad_offset);
-  }
-  if (!r && (which & 4)) {  // lane centres and scalars (the centres are kept: lanes may continue)
-    const size_t bytes = (size_t)ctx->lanes_alloc * 32;
-    r = move_buffer(ctx, reinterpret_cast<void **>(&ctx->d_cx), bytes, 0);
-    if (!r) r = move_buffer(ctx, reinterpret_cast<void **>(&ctx->d_cy), bytes, 0);
-    if (!r) r = move_buffer(ctx, reinterpret_cast<void **>(&ctx->d_scalars), bytes, 0);
-  }
-  if (!r && (which & 8)) {  // the walks' delta tables
-    for (auto &t : ctx->tables) {
-      const size_t H = (size_t)atoi(t.first.c_str() + 32);  // key: 32 scalar bytes, then "H/jump"
-      void *q = t.second;
-      r = move_buffer(ctx, &q, (H + 1) * 16 * 4, 0);
-      if (r) break;
-      t.second = static_cast<uint32_t *>(q);
-    }
-  }
-  if (!r && (which & 32)) {  // the walk's stream: a new one (another hardware queue), then the old one destroyed
-    hipStream_t ns = nullptr;
-    HIPCHK(ctx, hipStreamCreateWithFlags(&ns, hipStreamNonBlocking));
-    (void)hipStreamDestroy(ctx->stream);
-    ctx->stream = ns;
-  }
-  if (!r && (which & 16)) {  // layers 2 and 3
-    for (int l = 1; l < 3 && !r; l++)
-      r = move_buffer(ctx, reinterpret_cast<void **>(&ctx->d_bl[l]), 256 * ctx->bd[l].stride + 4, 0);
-  }
-  return r;
-}
-
-int kh_debug_burn(kh_ctx *ctx, double ms) {
-  if (!ctx || !(ms > 0)) return KH_E_ARG;
-  (void)hipSetDevice(ctx->device);
-  uint32_t *sink = ctx->d_zero_flag;
-  const uint32_t iters = 1u << 16;
-  HIPCHK(ctx, hipEventRecord(ctx->ev_a, ctx->stream));
-  HIPCHK(ctx, launch_burn(iters, sink, ctx->stream));
-  HIPCHK(ctx, hipEventRecord(ctx->ev_b, ctx->stream));
-  HIPCHK(ctx, hipEventSynchronize(ctx->ev_b));
-  float one = 0;
-  (void)hipEventElapsedTime(&one, ctx->ev_a, ctx->ev_b);
-  const int more = one > 0 ? (int)std::min(10000.0, ms / one) : 0;
-  for (int k = 1; k < more; k++) HIPCHK(ctx, launch_burn(iters, sink, ctx->stream));  // left in flight
-  ctx->burn_ms = one * std::max(1, more);
-  return KH_OK;
-}
-
-int kh_debug_layout(kh_ctx *ctx, uint64_t out[8]) {
-  if (!ctx || !out) return KH_E_ARG;
-  out[0] = (uint64_t)(uintptr_t)ctx->d_bl[0];
-  out[1] = ctx->d_bl[0] ? 256 * ctx->bd[0].stride + 4 : 0;
-  out[2] = (uint64_t)(uintptr_t)ctx->d_scratch;
-  out[3] = (uint64_t)ctx->lanes_alloc * ctx->scratch_h * 32;
-  out[4] = (uint64_t)(uintptr_t)ctx->d_bl[1];
-  out[5] = ctx->d_bl[1] ? 256 * ctx->bd[1].stride + 4 : 0;
-  out[6] = ctx->lanes_alloc;
-  out[7] = (uint64_t)ctx->scratch_h;
-  return KH_OK;
 }
 
 int kh_set_geometry(kh_ctx *ctx, uint32_t lanes, uint32_t groups_per_launch) {
@@ -970,7 +830,6 @@ int kh_set_geometry(kh_ctx *ctx, uint32_t lanes, uint32_t groups_per_launch) {
   // an explicit geometry overrides an earlier calibration's pick (and a default one calibrates again)
   ctx->lanes_pick = 0;
   ctx->bsgs_calibrated = false;
-  ctx->cal_stage = 0;
   for (double &x : ctx->cal_rate) x = 0;
   return KH_OK;
 }
@@ -1210,8 +1069,6 @@ int kh_scan(kh_ctx *ctx, const uint8_t start[32], const uint8_t stride_be[32], u
   A.cy = ctx->d_cy;
   A.scratch = ctx->d_scratch;
   A.L = jg.L;
-  A.pad_skew = ctx->pad_skew;
-  A.pad_swz = pad_swizzle(A.L);
   A.lane_stride = jg.gpl * 2 * H;
   A.interleave = inter ? 1 : 0;
   A.n_points = n_points;
@@ -1443,10 +1300,7 @@ int kh_bsgs_setup(kh_ctx *ctx, uint64_t n, uint64_t k, kh_bsgs_info *info) {
     size_t bytes = 256 * ctx->bd[l].stride + 4;
     // (fine-grained and uncached memory types for layer 1 were measured in round 4: no gain, the
     // probes still cost the same power, profiles/r04e_alloc_ab.json)
-    if (l == 0)
-      HIPCHK(ctx, dev_alloc(reinterpret_cast<void **>(&ctx->d_bl[l]), bytes, 1));
-    else
-      HIPCHK(ctx, hipMalloc(&ctx->d_bl[l], bytes));
+    HIPCHK(ctx, hipMalloc(&ctx->d_bl[l], bytes));
     HIPCHK(ctx, hipMemset(ctx->d_bl[l], 0, bytes));
   }
   // AMP2[i] = -(M2 + 2i*M2)G, AMP3[i] = -(M3 + 2i*M3)G  (keyhunt.cpp:1818-1842)
@@ -1519,8 +1373,6 @@ int build_walk(kh_ctx *ctx, int mode, uint8_t *bl1, const bloom_desc &bd1, uint6
   A.cy = ctx->d_cy;
   A.scratch = ctx->d_scratch;
   A.L = jg.L;
-  A.pad_skew = ctx->pad_skew;
-  A.pad_swz = pad_swizzle(A.L);
   A.lane_stride = jg.gpl * 2 * H;
   A.n_points = count;
   A.bl1 = bl1;
@@ -2393,8 +2245,6 @@ static int bsgs_scan_one(kh_ctx *ctx, const u256 &st, const std::vector<u256> *l
       Aw.cy = ctx->d_cy;
       Aw.scratch = ctx->d_scratch;
       Aw.L = jg.L;
-      Aw.pad_skew = ctx->pad_skew;
-      Aw.pad_swz = pad_swizzle(Aw.L);
       Aw.lane_stride = jg.gpl * 2 * H;
       Aw.interleave = cont ? 1 : 0;
       Aw.n_points = cont ? total_groups * 2 * H : rg * 2 * H;
@@ -2591,186 +2441,13 @@ static int bsgs_scan_one(kh_ctx *ctx, const u256 &st, const std::vector<u256> *l
 // on another, with identical instruction and request counts; the slow placements show only longer L2
 // request latencies in cycles at a higher clock (DESIGN.md §2 "Placement", profiles/r06f_state_counters.json,
 // r06j_buffer_replacement.json).  A context's first continuous call of at least 2^23 walk groups therefore
-// calibrates: it walks the call's parts on candidate placements in the order A B B A (A B C C B A, ...),
-// so a linear drift of clock or power cancels, times each part on the walk's events and keeps the faster.
-// The default candidates are 2^21 and 2^20 lanes on the one pad (2^20 lanes walk its first half: other
+// calibrates: it walks the call's four parts on two candidate placements in the order A B B A, so a
+// linear drift of clock or power cancels, times each part on the walk's events and keeps the faster.
+// The candidates are 2^21 and 2^20 lanes on the one pad (2^20 lanes walk its first half: other
 // physical pages) -- the form that measured best over five boxes (profiles/r06n..r06q_calibration_ab.json:
-// 41.2 G giant points/s mean against 40.7 uncalibrated, never below 39.4).  Opt-in stages, measured no
-// better: KH_PAD_CANDIDATES=N (N pads of the same size held at once, each at 2^21 lanes; with
-// KH_CAL_LANES=1 the primary at 2^20 lanes too), KH_CAL_STAGES=2 (then a stage over layer 1: a copy in a
-// new allocation), KH_CAL_MOVE=1 (the pad moved once or twice instead), KH_CAL_DEFER=N (the first N calls
-// uncalibrated).  Neither buffer holds state across launches that a swap could break: the pad is
-// rewritten by every group and the layer-1 copies are identical, so the lanes run on through the swaps.
+// 41.2 G giant points/s mean against 40.7 uncalibrated, never below 39.4).
 // KH_BSGS_CALIBRATE=0, KH_BSGS_LANES or kh_set_geometry's lanes switch the calibration off.  Every base
 // is walked once either way, so keys and candidates are those of an uncalibrated call.
-static constexpr int KH_CAL_SKIP = 1000;  // cal_stage: nothing walked, no candidate fits
-struct cal_slot {
-  void *base;  // the allocation (freed when the slot loses)
-  void *ptr;   // what the walk reads (the pad: base + KH_PAD_OFFSET)
-};
-static void cal_swap(kh_ctx *ctx, int stage, cal_slot &c) {
-  if (stage == 0) {
-    std::swap(ctx->d_scratch_base, c.base);
-    void *p = ctx->d_scratch;
-    ctx->d_scratch = static_cast<uint4 *>(c.ptr);
-    c.ptr = p;
-  } else {
-    void *p = ctx->d_bl[0];
-    ctx->d_bl[0] = static_cast<uint8_t *>(c.ptr);
-    c.ptr = p;
-    c.base = p;
-  }
-}
-// one calibration stage over the n_bases bases from st; returns the walk's status, hits in found
-static int cal_stage(kh_ctx *ctx, int stage, const u256 &st, uint64_t n_bases, kh_bsgs_found *found, uint32_t cap,
-                     uint32_t *n_found) {
-  const kh_bsgs_info &I = ctx->info;
-  const uint32_t hi = ctx->lanes_bsgs, lo = ctx->lanes_bsgs / 2;
-  const uint64_t gpb = I.cycles * 1024 / (2 * KH_WALK_HB);
-  const uint64_t rows = walk_pad_rows(KM_BSGSB, false, KH_WALK_HB);
-  struct cand {
-    int slot;  // 0: the primary (in ctx), k: slots[k]
-    uint32_t lanes;
-    double ms, pts;
-  };
-  std::vector<cand> cands{{0, hi, 0, 0}};
-  std::vector<cal_slot> slots(1, cal_slot{nullptr, nullptr});
-  size_t fr = 0, tot = 0;
-  if (stage == 0) {
-    const char *ncand = getenv("KH_PAD_CANDIDATES");
-    const int want = std::max(1, std::min(4, ncand ? atoi(ncand) : 1));
-    const uint64_t pad_bytes = ((uint64_t)hi + ctx->pad_skew) * rows * 32 + ctx->pad_offset;
-    for (int k = 1; k < want; k++) {
-      void *b = nullptr;
-      if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < pad_bytes + (32ull << 30) ||
-          dev_alloc(&b, pad_bytes, 2) != hipSuccess) {
-        (void)hipGetLastError();
-        break;
-      }
-      slots.push_back({b, static_cast<uint8_t *>(b) + ctx->pad_offset});
-      cands.push_back({(int)slots.size() - 1, hi, 0, 0});
-    }
-    // one pad (or KH_CAL_LANES=1): 2^20 lanes, which walk the first half of the primary pad
-    const char *cl = getenv("KH_CAL_LANES");
-    if (cands.size() == 1 || (cl && atoi(cl))) cands.push_back({0, lo, 0, 0});
-  } else {
-    const size_t bytes = 256 * ctx->bd[0].stride + 4;
-    void *b = nullptr;
-    if (hipMemGetInfo(&fr, &tot) == hipSuccess && fr >= bytes + (32ull << 30) && dev_alloc(&b, bytes, 1) == hipSuccess &&
-        hipMemcpy(b, ctx->d_bl[0], bytes, hipMemcpyDeviceToDevice) == hipSuccess) {
-      slots.push_back({b, b});
-      cands.push_back({1, hi, 0, 0});
-    } else {
-      (void)hipGetLastError();
-      if (b) (void)hipFree(b);
-      return KH_CAL_SKIP;  // no room for a copy: the stage is skipped
-    }
-  }
-  const int nc = (int)cands.size();
-  std::vector<int> order;
-  for (int k = 0; k < nc; k++) order.push_back(k);
-  for (int k = nc - 1; k >= 0; k--) order.push_back(k);
-  const uint64_t tile = std::max<uint64_t>(1, hi / std::max<uint64_t>(1, gpb));
-  const uint64_t nbq = std::max<uint64_t>(tile, (n_bases / order.size()) / tile * tile);
-  uint32_t nf_all = 0;
-  bool exact = true;
-  int r = KH_OK, cur = 0;
-  uint64_t done_b = 0;
-  for (size_t q = 0; q < order.size() && done_b < n_bases; q++) {
-    cand &c = cands[order[q]];
-    const uint64_t nb = q + 1 == order.size() ? n_bases - done_b : std::min(nbq, n_bases - done_b);
-    const u256 s = sc_add(st, sc_reduce(u256_from_u128((u128)done_b * 2 * I.n)));
-    if (c.slot != cur) {  // swap the buffer under the running lanes (the walk is idle between calls)
-      (void)hipStreamSynchronize(ctx->stream);
-      (void)hipStreamSynchronize(ctx->side);
-      if (cur) cal_swap(ctx, stage, slots[cur]);  // the primary back
-      if (c.slot) cal_swap(ctx, stage, slots[c.slot]);
-      cur = c.slot;
-    }
-    ctx->lanes_force = c.lanes;
-    const timing t0 = ctx->tm[2];
-    uint32_t nf = 0;
-    const uint32_t off = std::min(nf_all, cap);
-    r = bsgs_scan_one(ctx, s, nullptr, nb, found ? found + off : nullptr, cap - off, &nf);
-    ctx->lanes_force = 0;
-    if (ctx->lanes_used != c.lanes) exact = false;
-    c.ms += ctx->tm[2].ms - t0.ms;
-    c.pts += (double)(ctx->tm[2].points - t0.points);
-    nf_all += nf;
-    done_b += nb;
-    if ((r && r != KH_E_OVERFLOW) || ctx->found[0]) break;  // an error, or the key ended the call
-  }
-  (void)hipStreamSynchronize(ctx->stream);
-  (void)hipStreamSynchronize(ctx->side);
-  int best = -1, timed = 0;
-  for (int k = 0; k < nc; k++) {
-    if (!(cands[k].ms > 0 && cands[k].pts > 0)) continue;
-    timed++;
-    if (best < 0 || cands[k].pts / cands[k].ms > cands[best].pts / cands[best].ms) best = k;
-  }
-  const bool decided = best >= 0 && timed == nc && exact && (r == KH_OK || r == KH_E_OVERFLOW);
-  const int keep = decided ? cands[best].slot : cur;
-  if (cur) cal_swap(ctx, stage, slots[cur]);     // the primary back in ctx
-  if (keep) cal_swap(ctx, stage, slots[keep]);   // the kept one into ctx, the primary into its slot
-  for (size_t k = 1; k < slots.size(); k++) (void)hipFree(slots[k].base);
-  *n_found = nf_all;
-  if (decided) {
-    if (stage == 0) ctx->lanes_pick = cands[best].lanes;
-    ctx->cal_rate[2 * stage] = cands[best].pts / cands[best].ms * 1e3;
-    ctx->cal_rate[2 * stage + 1] = 0;
-    for (int k = 0; k < nc; k++)
-      if (k != best) ctx->cal_rate[2 * stage + 1] = std::max(ctx->cal_rate[2 * stage + 1], cands[k].pts / cands[k].ms * 1e3);
-    ctx->cal_stage = stage + 1;
-  }
-  return r;
-}
-// KH_CAL_MOVE=1 (pad stage variant): walk a part on the current pad, move the pad (a new allocation
-// taken while the old one is held, then the old one freed), walk a part; if that was slower, move once
-// more and keep the third placement.  Parts of n_bases / 3 (whole tiles).
-static int cal_move(kh_ctx *ctx, const u256 &st, uint64_t n_bases, kh_bsgs_found *found, uint32_t cap,
-                    uint32_t *n_found) {
-  const kh_bsgs_info &I = ctx->info;
-  const uint32_t hi = ctx->lanes_bsgs;
-  const uint64_t gpb = I.cycles * 1024 / (2 * KH_WALK_HB);
-  const uint64_t tile = std::max<uint64_t>(1, hi / std::max<uint64_t>(1, gpb));
-  const uint64_t nbq = std::max<uint64_t>(tile, (n_bases / 3) / tile * tile);
-  double rate[3] = {0, 0, 0};
-  uint32_t nf_all = 0;
-  uint64_t done_b = 0;
-  int r = KH_OK;
-  for (int q = 0; q < 3 && done_b < n_bases; q++) {
-    if (q == 2 && rate[1] >= rate[0]) break;  // the moved pad is at least as fast: keep it
-    if (q > 0) {
-      (void)hipStreamSynchronize(ctx->stream);
-      (void)hipStreamSynchronize(ctx->side);
-      r = kh_debug_replace(ctx, 2);
-      if (r) return r;
-    }
-    const uint64_t nb = std::min(nbq, n_bases - done_b);
-    const u256 s = sc_add(st, sc_reduce(u256_from_u128((u128)done_b * 2 * I.n)));
-    ctx->lanes_force = hi;
-    const timing t0 = ctx->tm[2];
-    uint32_t nf = 0;
-    const uint32_t off = std::min(nf_all, cap);
-    r = bsgs_scan_one(ctx, s, nullptr, nb, found ? found + off : nullptr, cap - off, &nf);
-    ctx->lanes_force = 0;
-    const double ms = ctx->tm[2].ms - t0.ms, pts = (double)(ctx->tm[2].points - t0.points);
-    rate[q] = ms > 0 ? pts / ms * 1e3 : 0;
-    nf_all += nf;
-    done_b += nb;
-    if ((r && r != KH_E_OVERFLOW) || ctx->found[0]) break;
-  }
-  *n_found = nf_all;
-  if (rate[0] > 0 && rate[1] > 0) {
-    ctx->lanes_pick = hi;
-    ctx->cal_rate[0] = rate[2] > 0 ? rate[2] : rate[1];
-    ctx->cal_rate[1] = rate[2] > 0 ? std::max(rate[0], rate[1]) : rate[0];
-    ctx->cal_stage = 1;
-  }
-  ctx->cal_moved_bases = done_b;
-  return r;
-}
-
 static int bsgs_scan_impl(kh_ctx *ctx, const u256 &st, const std::vector<u256> *list, uint64_t n_bases,
                           kh_bsgs_found *found, uint32_t cap, uint32_t *n_found) {
   if (!ctx->bsgs_built) return KH_E_STATE;
@@ -2779,91 +2456,63 @@ static int bsgs_scan_impl(kh_ctx *ctx, const u256 &st, const std::vector<u256> *
   const uint64_t gpb = A_pts / (2 * KH_WALK_HB);
   const uint32_t hi = ctx->lanes_bsgs, lo = ctx->lanes_bsgs / 2;
   const uint64_t tile = std::max<uint64_t>(1, hi / std::max<uint64_t>(1, gpb));  // bases per 2^21 groups
-  // KH_BURN_MS=<ms>: before the context's first large call, that long a VALU-dense load on the walk's
-  // stream, enqueued right ahead of the walk (A/B knob for the clock/latency operating point)
-  if (!ctx->burned && n_bases * gpb >= hi) {
-    ctx->burned = true;
-    const char *bm = getenv("KH_BURN_MS");
-    const double want_ms = bm ? atof(bm) : 0.0;
-    if (want_ms > 0) {
-      const int rb = kh_debug_burn(ctx, want_ms);
-      if (rb) return rb;
-    }
-  }
   const char *cal = getenv("KH_BSGS_CALIBRATE");
   const bool calibrate = !ctx->bsgs_calibrated && !list && A_pts == I.aux && A_pts % (2 * KH_WALK_HB) == 0 &&
                          hi == KH_BSGS_LANES && lo > ctx->lanes_max && !(cal && atoi(cal) == 0) &&
                          !getenv("KH_BSGS_LANES") && !getenv("KH_BSGS_NARROW") && !getenv("KH_NO_BIG_GROUPS") &&
                          n_bases * gpb >= 4ull * hi && ctx->targets.size() == 1 && !ctx->found[0];
   if (!calibrate) return bsgs_scan_one(ctx, st, list, n_bases, found, cap, n_found);
-  // KH_CAL_DEFER=N: the first N eligible calls walk uncalibrated (the board settles into its power-capped
-  // operating point first)
-  const char *dfr = getenv("KH_CAL_DEFER");
-  if (dfr && ctx->cal_deferred < (uint32_t)atoi(dfr)) {
-    ctx->cal_deferred++;
-    return bsgs_scan_one(ctx, st, list, n_bases, found, cap, n_found);
-  }
-  // the primary pad at 2^21 lanes first (bsgs_scan_one would take it too): with no room, no calibration
+  // the pad at 2^21 lanes first (bsgs_scan_one would take it too): with no room, or with fewer than four
+  // tiles of bases (a base of more than 2^21 groups), no calibration
   {
     size_t fr = 0, tot = 0;
     const uint64_t lane_bytes = (uint64_t)hi * (walk_pad_rows(KM_BSGSB, false, KH_WALK_HB) * 32 + 96);
     const uint64_t have = ctx->lanes_alloc >= hi ? lane_bytes : 0;
     if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr + have < lane_bytes + (32ull << 30) ||
-        ensure_pipeline(ctx, hi, KH_WALK_HB) != KH_OK) {
+        ensure_pipeline(ctx, hi, KH_WALK_HB) != KH_OK || n_bases < 4 * tile) {
       (void)hipGetLastError();
       ctx->err.clear();
       return bsgs_scan_one(ctx, st, list, n_bases, found, cap, n_found);
     }
   }
+  const uint32_t lanes[4] = {hi, lo, lo, hi};
+  double ms[2] = {0, 0}, pts[2] = {0, 0};  // [0]: hi, [1]: lo
+  const uint64_t nbq = std::max<uint64_t>(tile, (n_bases / 4) / tile * tile);
   uint32_t nf_all = 0;
   uint64_t done_b = 0;
+  bool exact = true;
   int r = KH_OK;
-  // stages while the call has 4 tiles left for one (the last stage of the call takes the rest of it);
-  // KH_CAL_STAGES=1: the pad stage only
-  const char *nst = getenv("KH_CAL_STAGES");
-  const int stages = std::max(1, std::min(2, nst ? atoi(nst) : 1));
-  if (ctx->cal_stage >= stages) ctx->cal_stage = 2;
-  while (ctx->cal_stage < stages && (n_bases - done_b) >= 4 * tile && !ctx->found[0]) {
-    const uint64_t left = n_bases - done_b;
-    // with a second stage to come, the first takes half of a call that holds both
-    const uint64_t nb = ctx->cal_stage == 0 && stages > 1 && left >= 8 * tile ? left / 2 / tile * tile : left;
+  for (int q = 0; q < 4 && done_b < n_bases; q++) {
+    const int k = lanes[q] == lo;
+    const uint64_t nb = q == 3 ? n_bases - done_b : std::min(nbq, n_bases - done_b);
     const u256 s = sc_add(st, sc_reduce(u256_from_u128((u128)done_b * 2 * I.n)));
+    ctx->lanes_force = lanes[q];
+    const timing t0 = ctx->tm[2];
     uint32_t nf = 0;
     const uint32_t off = std::min(nf_all, cap);
-    const int stage = ctx->cal_stage;
-    const char *mv = getenv("KH_CAL_MOVE");
-    uint64_t walked = nb;
-    if (stage == 0 && mv && atoi(mv)) {
-      r = cal_move(ctx, s, nb, found ? found + off : nullptr, cap - off, &nf);
-      walked = ctx->cal_moved_bases;
-    } else {
-      r = cal_stage(ctx, stage, s, nb, found ? found + off : nullptr, cap - off, &nf);
-    }
-    if (r == KH_CAL_SKIP) {  // no room for the stage's candidate: calibration ends here
-      r = KH_OK;
-      ctx->cal_stage = 2;
-      break;
-    }
+    r = bsgs_scan_one(ctx, s, nullptr, nb, found ? found + off : nullptr, cap - off, &nf);
+    ctx->lanes_force = 0;
+    if (ctx->lanes_used != lanes[q]) exact = false;
+    ms[k] += ctx->tm[2].ms - t0.ms;
+    pts[k] += (double)(ctx->tm[2].points - t0.points);
     nf_all += nf;
-    done_b += walked;
-    if (r && r != KH_E_OVERFLOW) return r;
-    if (ctx->cal_stage == stage) {  // undecided: the key ended the call (try again next call), or a
-      if (!ctx->found[0]) ctx->cal_stage = 2;  // part could not take its lane count (give up)
-      break;
-    }
+    done_b += nb;
+    if ((r && r != KH_E_OVERFLOW) || ctx->found[0]) break;  // an error, or the key ended the call
   }
-  if (ctx->cal_stage >= stages) ctx->bsgs_calibrated = true;
-  if (done_b < n_bases && !ctx->found[0] && (r == KH_OK || r == KH_E_OVERFLOW)) {
-    const u256 s = sc_add(st, sc_reduce(u256_from_u128((u128)done_b * 2 * I.n)));
-    uint32_t nf = 0;
-    const uint32_t off = std::min(nf_all, cap);
-    const int r2 = bsgs_scan_one(ctx, s, nullptr, n_bases - done_b, found ? found + off : nullptr, cap - off, &nf);
-    nf_all += nf;
-    if (r2 && r2 != KH_E_OVERFLOW) return r2;
-    if (r2) r = r2;
-  }
+  (void)hipStreamSynchronize(ctx->stream);
+  (void)hipStreamSynchronize(ctx->side);
   *n_found = nf_all;
-  return *n_found > cap ? KH_E_OVERFLOW : r;
+  if (r && r != KH_E_OVERFLOW) return r;
+  if (exact && ms[0] > 0 && pts[0] > 0 && ms[1] > 0 && pts[1] > 0) {
+    const int best = pts[1] / ms[1] > pts[0] / ms[0];
+    ctx->lanes_pick = best ? lo : hi;
+    ctx->cal_rate[0] = pts[best] / ms[best] * 1e3;
+    ctx->cal_rate[1] = pts[!best] / ms[!best] * 1e3;
+    ctx->bsgs_calibrated = true;
+  } else if (!ctx->found[0]) {  // a part could not take its lane count: give up (lanes_pick stays 0);
+    ctx->bsgs_calibrated = true;  // when the key ended the call, the next eligible call calibrates
+  }
+  return nf_all > cap ? KH_E_OVERFLOW : r;
 }
 
 int kh_bsgs_scan(kh_ctx *ctx, const uint8_t start[32], uint64_t n_bases, kh_bsgs_found *found, uint32_t cap,
@@ -3105,8 +2754,6 @@ int kh_walk_points(kh_ctx *ctx, const uint8_t start[32], const uint8_t stride_be
   A.cy = ctx->d_cy;
   A.scratch = ctx->d_scratch;
   A.L = jg.L;
-  A.pad_skew = ctx->pad_skew;
-  A.pad_swz = pad_swizzle(A.L);
   A.lane_stride = jg.gpl * 2 * H;
   A.n_points = n_points;
   A.dump_x = dx;

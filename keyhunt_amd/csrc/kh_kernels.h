@@ -141,9 +141,6 @@ KH_HD void kh_blk_masks(uint32_t s0, uint32_t s1, uint32_t s2, uint32_t m[4]) {
 #ifndef KH_PAD_PLANES
 #define KH_PAD_PLANES 0
 #endif
-#ifndef KH_PAD_KNOBS
-#define KH_PAD_KNOBS 0  // kernel side of the KH_PAD_SKEW / KH_PAD_SWZ pad-layout A/B knobs
-#endif
 //   KH_PAD_NT      the inversion pad's stores (bit 0) / loads (bit 1) with the nontemporal hint
 #ifndef KH_PAD_NT
 #define KH_PAD_NT 0
@@ -231,11 +228,6 @@ struct walk_args {
   uint32_t *dump_x, *dump_y;
   // k_walk_zinv: half of the --rmd-batch-size group (groups of 2 * zhalf slots)
   uint32_t zhalf;
-  // inversion pad: lanes of gap after each row (row stride L + pad_skew entries; KH_PAD_SKEW A/B knob)
-  uint32_t pad_skew;
-  // inversion pad: row r keeps lane g's entry in column g ^ ((r & 7) << 8) (L a multiple of 2048), so
-  // the columns of one 256-lane workgroup -- one XCD's -- rotate over the 8 KB chunk classes row by row
-  uint32_t pad_swz;
 };
 
 struct setup_args {
@@ -293,7 +285,6 @@ inline int walk_pad_rows(int mode, bool tblk, int H) {
 }
 hipError_t launch_walk_zinv(int mode, const walk_args &A, hipStream_t st);
 hipError_t launch_refine(const refine_args &A, hipStream_t st);
-hipError_t launch_burn(uint32_t iters, uint32_t *sink, hipStream_t st);
 hipError_t launch_setup(const setup_args &A, hipStream_t st);
 hipError_t launch_test_hash160(const uint32_t *xs, const uint32_t *ys, uint32_t n, uint32_t *out, hipStream_t st);
 hipError_t launch_test_field(const uint32_t *a, const uint32_t *b, uint32_t n, uint32_t *out, hipStream_t st);

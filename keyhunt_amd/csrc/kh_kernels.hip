@@ -569,10 +569,6 @@ __global__ void __launch_bounds__((walk_threads<MODE, H>()), (walk_blocks_per_cu
   };
   uint4 *__restrict__ scr = A.scratch;
   const size_t L = A.L;
-  // the pad's row stride in lane entries; the row-skew and column-swizzle A/B knobs (KH_PAD_SKEW,
-  // KH_PAD_SWZ: no effect on the rate, DESIGN.md §2 "Placement") cost ~1 VALU per point, so they are
-  // compiled in only with -DKH_PAD_KNOBS=1
-  const size_t LS = KH_PAD_KNOBS ? L + A.pad_skew : L;
   fe cx, cy;
   load_soa(cx, A.cx, A.L, g);
   load_soa(cy, A.cy, A.L, g);
@@ -587,14 +583,14 @@ __global__ void __launch_bounds__((walk_threads<MODE, H>()), (walk_blocks_per_cu
   // HBM traffic (outputs wrong)
   auto fold = [&](int m, int which) {
     const int r = SPARSE ? (m >> 1) : m;
-    return (size_t)((KH_TIMING_PAD_FOLD & which) ? (r & ((1 << KH_TIMING_PAD_ROWS_LOG2) - 1)) : r) * LS + g;
+    return (size_t)((KH_TIMING_PAD_FOLD & which) ? (r & ((1 << KH_TIMING_PAD_ROWS_LOG2) - 1)) : r) * L + g;
   };
   auto slot_w = [&](int m) { return fold(m, 1); };
   auto slot = [&](int m) { return fold(m, 2); };
 #else
   auto slot = [&](int m) {
     const uint32_t r = SPARSE ? (uint32_t)(m >> 1) : (uint32_t)m;
-    return (size_t)r * LS + (KH_PAD_KNOBS && A.pad_swz ? (g ^ ((r & 7u) << 8)) : g);
+    return (size_t)r * L + g;
   };
   auto slot_w = slot;
 #endif
@@ -1357,29 +1353,6 @@ hipError_t launch_walk_zinv(int mode, const walk_args &A, hipStream_t st) {
   }
   return hipGetLastError();
 #endif
-}
-
-// A VALU-dense load (multiply-add chains, no memory traffic) run right before a BSGS job's first walk
-// launch (KH_BURN_MS, kh_capi.cpp): it drives the board's clock down to its power cap before the walk
-// starts, so the walk settles into the low-clock operating point (DESIGN.md §2 "Placement")
-__global__ void __launch_bounds__(256) k_burn(uint32_t iters, uint32_t *sink) {
-  uint64_t a[8];
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < 8; k++) a[k] = (uint64_t)(g * 2654435761u + k) | 1;
-  for (uint32_t i = 0; i < iters; i++) {
-#pragma unroll
-    for (int k = 0; k < 8; k++) a[k] = (uint64_t)(uint32_t)a[k] * (uint32_t)(a[k] >> 17) + a[(k + 1) & 7];
-  }
-  uint64_t x = 0;
-#pragma unroll
-  for (int k = 0; k < 8; k++) x ^= a[k];
-  if (x == 0x0123456789ABCDEFull) sink[0] = g;  // never in practice: keeps the chains live
-}
-
-hipError_t launch_burn(uint32_t iters, uint32_t *sink, hipStream_t st) {
-  hipLaunchKernelGGL(k_burn, dim3(256 * 8), dim3(256), 0, st, iters, sink);
-  return hipGetLastError();
 }
 
 hipError_t launch_refine(const refine_args &A, hipStream_t st) {

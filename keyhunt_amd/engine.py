@@ -78,10 +78,7 @@ def lib() -> ctypes.CDLL:
     L.kh_close.argtypes = [P]
     L.kh_set_geometry.argtypes = [P, ctypes.c_uint32, ctypes.c_uint32]
     L.kh_release_walk.argtypes = [P]
-    L.kh_debug_layout.argtypes = [P, ctypes.POINTER(ctypes.c_uint64 * 8)]
     L.kh_bsgs_placement.argtypes = [P, ctypes.POINTER(ctypes.c_double * 4)]
-    L.kh_debug_replace.argtypes = [P, ctypes.c_uint32]
-    L.kh_debug_burn.argtypes = [P, ctypes.c_double]
     L.kh_bsgs_geometry.argtypes = [P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_double * 2)]
     L.kh_synchronize.argtypes = [P]
     L.kh_scan_memory.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]
@@ -179,33 +176,14 @@ class Engine:
         self._chk(lib().kh_set_geometry(self._ctx, lanes, groups_per_launch), "kh_set_geometry")
 
     def bsgs_geometry(self) -> tuple[int, float, float]:
-        """(lanes kept for large BSGS calls or 0, giant points/s of the pad placement kept, of the best
-        other candidate) -- the context's placement calibration (kh_bsgs_geometry)."""
+        """(lanes kept for large BSGS calls or 0, giant points/s of the lane count kept, of the other
+        one) -- the context's placement calibration (kh_bsgs_geometry)."""
         lanes, rates = ctypes.c_uint32(), (ctypes.c_double * 2)()
         self._chk(lib().kh_bsgs_geometry(self._ctx, ctypes.byref(lanes), ctypes.byref(rates)), "kh_bsgs_geometry")
         return lanes.value, rates[0], rates[1]
 
-    def debug_layout(self) -> dict:
-        """Device addresses and sizes of layer 1, the inversion pad and layer 2 (kh_debug_layout)."""
-        o = (ctypes.c_uint64 * 8)()
-        self._chk(lib().kh_debug_layout(self._ctx, ctypes.byref(o)), "kh_debug_layout")
-        return {"layer1": [hex(o[0]), o[1]], "pad": [hex(o[2]), o[3]], "layer2": [hex(o[4]), o[5]],
-                "lanes": o[6], "pad_rows": o[7]}
-
-    def debug_replace(self, which: int) -> None:
-        """Give device buffers fresh allocations (kh_debug_replace; diagnostics): 1 layer 1, 2 the pad,
-        4 the lane arrays, 8 the delta tables, 16 layers 2 and 3."""
-        self._chk(lib().kh_debug_replace(self._ctx, which), "kh_debug_replace")
-
-    def debug_burn(self, ms: float) -> None:
-        """Enqueue ~ms of VALU-dense load on the walk's stream (kh_debug_burn; diagnostics)."""
-        self._chk(lib().kh_debug_burn(self._ctx, ms), "kh_debug_burn")
-
-    def debug_replace_layer1(self) -> None:
-        self.debug_replace(1)
-
     def bsgs_placement(self) -> tuple[bool, list[float]]:
-        """(calibration complete, [pad kept, pad other, layer-1 kept, layer-1 other] giant points/s)."""
+        """(calibration complete, [lanes kept, lanes other, 0.0, 0.0] giant points/s)."""
         rates = (ctypes.c_double * 4)()
         r = lib().kh_bsgs_placement(self._ctx, ctypes.byref(rates))
         if r < 0:

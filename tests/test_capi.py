@@ -3,6 +3,7 @@ host-side argument checking works without touching a GPU."""
 import ctypes
 import os
 import re
+import shutil
 import subprocess
 
 import pytest
@@ -17,6 +18,14 @@ def test_library_exports_every_header_symbol():
     assert len(syms) >= 25
     for s in syms:
         assert hasattr(L, s), s
+
+
+def test_library_exports_nothing_but_header_symbols():
+    """The other direction: every kh_* function the library defines is declared in the header."""
+    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    out = subprocess.run([nm, "-D", "--defined-only", E.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    names = {ln.split()[-1] for ln in out.splitlines() if ln.split()}
+    assert {s for s in names if re.match(r"^kh_[a-z0-9_]+$", s)} == set(keyhunt_amd.header_symbols())
 
 
 def test_abi_version_and_errors():

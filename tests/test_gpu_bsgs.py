@@ -483,24 +483,16 @@ def test_calls_with_ragged_lane_tiles(oracle, lanes, calls):
     assert res[1][0] == res[3][0] == [(0, key)]
 
 
-@pytest.mark.parametrize("cands,stages", [(1, 1), (2, 2), (3, 2), ("move", 1)])
-def test_placement_calibration_same_results(oracle, monkeypatch, cands, stages):
-    """A context's first call of >= 2^23 walk groups walks its parts on candidate placements and keeps the
-    fastest: by default 2^21 and 2^20 lanes on the one pad (A B B A); opt-in, several pads held at once
-    (KH_PAD_CANDIDATES, A B C C B A) then a layer-1 copy (KH_CAL_STAGES=2), or the pad moved
-    (KH_CAL_MOVE=1).  The same first-level candidates and walked points as an uncalibrated call
-    (KH_BSGS_CALIBRATE=0), the key found in any part, and kh_bsgs_geometry / kh_bsgs_placement report the
-    kept and the best other candidates' rates."""
+def test_placement_calibration_same_results(oracle, monkeypatch):
+    """A context's first call of >= 2^23 walk groups walks its four parts at 2^21, 2^20, 2^20 and 2^21
+    lanes on the one pad (A B B A) and keeps the faster.  The same first-level candidates and walked
+    points as an uncalibrated call (KH_BSGS_CALIBRATE=0), the key found in any part, and
+    kh_bsgs_geometry / kh_bsgs_placement report the kept and the other candidate's rates."""
     import keyhunt_amd as K
     p = oracle.bsgs_params(N36, K16)
-    nb = 1 << 22                           # 4 groups per base: 8 x 2^21 groups, both stages in one call
+    nb = 1 << 22                           # 4 groups per base: 8 x 2^21 groups
     start = 0x3C3C3C3C3C000000
     far = start - 777 * 2 * p.n
-    if cands == "move":
-        monkeypatch.setenv("KH_CAL_MOVE", "1")
-    else:
-        monkeypatch.setenv("KH_PAD_CANDIDATES", str(cands))
-    monkeypatch.setenv("KH_CAL_STAGES", str(stages))
     res = []
     for calibrate in (True, False):
         if calibrate:
@@ -518,10 +510,10 @@ def test_placement_calibration_same_results(oracle, monkeypatch, cands, stages):
     assert res[0][1] == res[1][1] == nb * p.aux
     lanes, r_kept, r_other = res[0][2]
     assert lanes in (1 << 21, 1 << 20) and r_kept > 0 and r_other > 0
-    assert cands == "move" or r_kept >= r_other   # a move keeps its last placement whatever it measured
+    assert r_kept >= r_other
     done, rates = res[0][3]
     assert done and rates[0] == r_kept
-    assert (rates[2] >= rates[3] > 0) if stages == 2 else rates[2:] == [0.0, 0.0]
+    assert rates[2:] == [0.0, 0.0]
     assert res[1][2] == (0, 0.0, 0.0) and res[1][3] == (False, [0.0] * 4)
     monkeypatch.delenv("KH_BSGS_CALIBRATE", raising=False)
     for where in (3, nb // 2 - 7, nb - 5):  # the key in the first, a middle and the last part
@@ -535,7 +527,8 @@ def test_placement_calibration_same_results(oracle, monkeypatch, cands, stages):
 
 def test_release_walk_between_calls(engine, oracle):
     """kh_release_walk frees the lane arrays and the pad: the next call allocates them again and
-    starts its lanes afresh, with the same candidates, walked points and key as uninterrupted calls."""
+    starts its lanes afresh, with the same candidates, walked points and key as uninterrupted calls.
+    An xpoint chunk on the same context after the BSGS walks finds its keys."""
     import keyhunt_amd as K
     p = oracle.bsgs_params(N36, K16)
     engine.bsgs_setup(N36, K16, layer1=K.KH_LAYER1_BLOCKED)
@@ -556,6 +549,10 @@ def test_release_walk_between_calls(engine, oracle):
             res.append((got, engine.bsgs_candidates() - c0, _walked(engine)))
     assert res[0] == res[1] and res[0][0] == [] and res[0][1] > 0 and res[0][2] == 4096 * p.aux
     assert res[2][:2] == res[3][:2] and res[2][0] == [(0, key)]
+    xkeys = [(1 << 61) + 12345 + 99991 * j for j in range(5)]
+    engine.set_targets([oracle.pubkey(k)[0].to_bytes(32, "big")[:20] for k in xkeys])
+    xs = engine.scan(1 << 61, 1 << 24, mode=K.KH_MODE_XPOINT, search=0)
+    assert sorted(h.key for h in xs) == sorted(xkeys)
 
 
 def test_bsgs_lanes_continue_across_calls(engine, oracle):
@@ -604,34 +601,3 @@ def test_bsgs_lanes_continue_across_calls(engine, oracle):
             if plan == [1024] * 4:             # the lanes were started once, then continued
                 assert engine.kernel_time(TIME_SETUP)[0] == 1
             assert (engine.bsgs_candidates() - c0, _walked(engine)) == one_call, plan
-
-
-def test_pad_skew_and_offset_same_results(oracle, monkeypatch):
-    """The pad layout knobs (KH_PAD_SKEW: a gap of lanes after every pad row, honoured by the kernels of
-    a -DKH_PAD_KNOBS=1 build; KH_PAD_OFFSET: the pad's start inside its allocation) move only where the
-    inversion pad sits: the same first-level candidates, walked points and key as the default layout, for
-    the BSGS walk and an xpoint chunk."""
-    import keyhunt_amd as K
-    p = oracle.bsgs_params(N36, K16)
-    start = 0x7777777700000
-    key = start + 3000 * 2 * p.n + 31
-    xkeys = [(1 << 61) + 12345 + 99991 * j for j in range(5)]
-    xrows = [oracle.pubkey(k)[0].to_bytes(32, "big")[:20] for k in xkeys]
-    res = []
-    for skew, off in ((None, None), ("37", "4096"), ("3000", "65792")):
-        for var, val in (("KH_PAD_SKEW", skew), ("KH_PAD_OFFSET", off)):
-            if val is None:
-                monkeypatch.delenv(var, raising=False)
-            else:
-                monkeypatch.setenv(var, val)
-        with K.Engine(0) as e:
-            e.bsgs_setup(N36, K16, layer1=K.KH_LAYER1_BLOCKED)
-            e.bsgs_build()
-            e.bsgs_set_targets([oracle.pubkey(key)])
-            got = e.bsgs_scan(start, 4096)
-            walked = _walked(e)
-            e.set_targets(xrows)
-            xs = sorted(h.key for h in e.scan(1 << 61, 1 << 24, mode=K.KH_MODE_XPOINT, search=0))
-            res.append((got, e.bsgs_candidates(), walked, xs))
-    assert res[0][0] == [(0, key)] and res[0][1] > 0 and res[0][3] == sorted(xkeys)
-    assert res[1] == res[0] and res[2] == res[0]

@@ -1,11 +1,11 @@
 """Interleaved in-process A/B of walk-placement variants on the bench's BSGS geometry (n = 2^44, k = 128):
 for each trial, each variant frees the walk buffers (kh_release_walk), sets its environment (knobs the
-engine reads when it allocates or launches: KH_PAD_SKEW, KH_BSGS_LANES, ...), then walks --calls
+engine reads when it allocates or launches: KH_BSGS_LANES, KH_BSGS_NARROW, ...), then walks --calls
 kh_bsgs_scan calls of --bases bases; the first call after the re-allocation is untimed.  Variants
 alternate A B A B ..., so drift and the re-placement of the pad spread over all of them.
 
 usage: python tools/env_ab.py [--trials 4] [--calls 2] [--bases 4194304] NAME:VAR=VAL[,VAR=VAL] ...
-e.g.   python tools/env_ab.py base:KH_PAD_SKEW=0 skew64:KH_PAD_SKEW=64
+e.g.   python tools/env_ab.py l21:KH_BSGS_LANES=2097152 l20:KH_BSGS_LANES=1048576
 """
 import argparse
 import json
@@ -65,8 +65,7 @@ def main():
             bw = board.between(b0, b1) or {}
             r = {"trial": t, "variant": name, "env": env, "giant_points_per_s_wall": a.calls * pts_call / (t1 - t0),
                  "giant_points_per_s_events": pts / (ms / 1e3), "ms_per_launch": ms / max(1, la),
-                 "board": {k: bw.get(k) for k in ("board_gfxclk_mhz", "socket_power_w", "ppt_residency_frac")},
-                 "layout": e.debug_layout()}
+                 "board": {k: bw.get(k) for k in ("board_gfxclk_mhz", "socket_power_w", "ppt_residency_frac")}}
             r["points_per_joule"] = (r["giant_points_per_s_wall"] / bw["socket_power_w"]) if bw.get("socket_power_w") else None
             rows.append(r)
             print(json.dumps({"t": t, "v": name, "G": round(r["giant_points_per_s_wall"] / 1e9, 3),
