@@ -238,8 +238,28 @@ int kh_walk_points(kh_ctx *ctx, const uint8_t start[32], const uint8_t stride[32
 int kh_hash160(kh_ctx *ctx, const uint8_t *xy, uint32_t n, uint8_t *out60);
 /* field ops on the device: per pair (a,b) -> mul, sqr(a), inv(a), add, sub (5 x 32 B) */
 int kh_field_ops(kh_ctx *ctx, const uint8_t *a, const uint8_t *b, uint32_t n, uint8_t *out160);
-/* bloom_check of n items (len 20 or 32) against the target bloom (layer 0) or BSGS layer 1..3 */
+/* bloom_check of n items (len 20 or 32) against the target bloom (layer 0) or BSGS layer 1..3.  Layer 0
+ * also takes len 1..19: the items stay 20 bytes apart and the filter is keyed on their first len bytes,
+ * as a vanity walk probes it (kh_set_vanity's probe_len). */
 int kh_bloom_check(kh_ctx *ctx, uint32_t layer, const uint8_t *items, uint32_t n, uint32_t len, uint8_t *out);
+/* the same with both device probe forms side by side: out = the eager probe (both hashes up front, as
+ * kh_bloom_check), out_lazy = the walks' own probe, which stops at the first clear bit and computes
+ * the second hash only after bit 0 (the blocked layer 1 has one form: both are its answer) */
+int kh_bloom_check2(kh_ctx *ctx, uint32_t layer, const uint8_t *items, uint32_t n, uint32_t len, uint8_t *out,
+                    uint8_t *out_lazy);
+/* per input point, the digests as the walks compute them: hash160(02||X) and hash160(03||X) from the
+ * interleaved pair form, hash160(04||X||Y), the Ethereum address -> 80 bytes.  Any (x, y) is hashed,
+ * on the curve or not. */
+int kh_digests(kh_ctx *ctx, const uint8_t *xy, uint32_t n, uint8_t *out80);
+/* per 20-byte item, the filter key pair the walks derive from its first len (1..20) bytes:
+ * ab[2i] = XXH64(item[0..len), bloom seed), ab[2i+1] = XXH64(item[0..len), ab[2i]) */
+int kh_filter_keys(kh_ctx *ctx, const uint8_t *items, uint32_t n, uint32_t len, uint64_t *ab);
+/* the walks' probe of n 20-byte items against the blocked target filter of the exact targets
+ * (kh_set_targets / kh_targets_load); KH_E_STATE without exact targets */
+int kh_tblk_check(kh_ctx *ctx, const uint8_t *items, uint32_t n, uint8_t *out);
+/* the last kh_scan: the filter hits the device reported (before the host's exact confirmation), and
+ * how many times the scan grew its hit buffer and redid the chunk */
+int kh_scan_device_hits(kh_ctx *ctx, uint32_t *device_hits, uint32_t *redos);
 /* copy a bloom back: layer 0 = target bloom, 1..3 = BSGS layers (256 shards concatenated, unpadded) */
 int kh_get_bloom(kh_ctx *ctx, uint32_t layer, uint8_t *buf, uint64_t cap, uint64_t *bytes);
 /* The context's own sorted bP rows (16 B each, the reference's bsgs_xvalue layout), valid until the

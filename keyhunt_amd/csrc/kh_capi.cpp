@@ -364,6 +364,8 @@ struct kh_ctx {
   uint32_t *d_zero_flag = nullptr;  // k_setup's progression mode: a lane scalar was 0 mod n
   kh_dev_hit *d_hits = nullptr;
   std::vector<kh_dev_hit> h_hits;
+  uint32_t scan_dev_hits = 0;  // kh_scan_device_hits: filter hits the device reported in the last kh_scan ...
+  uint32_t scan_redos = 0;     // ... and how often that scan grew the hit buffer and redid its chunk
 
   // address targets
   std::vector<uint8_t> rows;  // sorted, 20 B each
@@ -1082,6 +1084,8 @@ int kh_scan(kh_ctx *ctx, const uint8_t start[32], const uint8_t stride_be[32], u
   A.hit_cap = ctx->hit_cap;
   A.probe_len = mode == KH_MODE_XPOINT || mode == KH_MODE_ETH ? 20 : ctx->probe_len;
   uint32_t nd = 0;
+  ctx->scan_dev_hits = 0;
+  ctx->scan_redos = 0;
   for (;;) {
     HIPCHK(ctx, hipMemsetAsync(ctx->d_hit_count, 0, 4, ctx->stream));
     r = run_walk(ctx, km, mode == KH_MODE_XPOINT ? 1 : 0, A, jg.gpl, 2, H);
@@ -1100,10 +1104,12 @@ int kh_scan(kh_ctx *ctx, const uint8_t start[32], const uint8_t stride_be[32], u
     ctx->hit_cap = (uint32_t)cap2;
     A.hits = ctx->d_hits;
     A.hit_cap = ctx->hit_cap;
+    ctx->scan_redos++;
     r = run_setup_prog(ctx, s0, lane_step, jg.L);  // the walk moved the lane centres on: start them again
     if (r) return r;
   }
   if (r) return r;
+  ctx->scan_dev_hits = nd;
   if (inter) {  // the lanes now sit on the chunk that starts at st + n_keys * stride
     u256 adv = u256_u64(0), x = stride;
     for (uint64_t k = n_keys; k; k >>= 1) {
@@ -2841,9 +2847,86 @@ int kh_field_ops(kh_ctx *ctx, const uint8_t *a, const uint8_t *b, uint32_t n, ui
   return KH_OK;
 }
 
-int kh_bloom_check(kh_ctx *ctx, uint32_t layer, const uint8_t *items, uint32_t n, uint32_t len, uint8_t *out) {
-  if (!ctx || !items || !out || !n || (len != 20 && len != 32) || layer > 3) return KH_E_ARG;
+int kh_digests(kh_ctx *ctx, const uint8_t *xy, uint32_t n, uint8_t *out80) {
+  if (!ctx || !xy || !out80 || !n) return KH_E_ARG;
   (void)hipSetDevice(ctx->device);
+  std::vector<uint32_t> hx((size_t)n * 8), hy((size_t)n * 8), ho((size_t)n * 20);
+  for (uint32_t i = 0; i < n; i++) {
+    fe x, y;
+    fe_from_be(x, xy + 64 * i);
+    fe_from_be(y, xy + 64 * i + 32);
+    memcpy(&hx[(size_t)i * 8], x.d, 32);
+    memcpy(&hy[(size_t)i * 8], y.d, 32);
+  }
+  uint32_t *dx, *dy, *dout;
+  HIPCHK(ctx, hipMalloc(&dx, hx.size() * 4));
+  HIPCHK(ctx, hipMalloc(&dy, hy.size() * 4));
+  HIPCHK(ctx, hipMalloc(&dout, ho.size() * 4));
+  HIPCHK(ctx, hipMemcpy(dx, hx.data(), hx.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMemcpy(dy, hy.data(), hy.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(ctx, launch_test_digests(dx, dy, n, dout, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpy(ho.data(), dout, ho.size() * 4, hipMemcpyDeviceToHost));
+  (void)hipFree(dx);
+  (void)hipFree(dy);
+  (void)hipFree(dout);
+  memcpy(out80, ho.data(), (size_t)n * 80);
+  return KH_OK;
+}
+
+int kh_filter_keys(kh_ctx *ctx, const uint8_t *items, uint32_t n, uint32_t len, uint64_t *ab) {
+  if (!ctx || !items || !ab || !n || len == 0 || len > 20) return KH_E_ARG;
+  (void)hipSetDevice(ctx->device);
+  uint8_t *ditems;
+  uint64_t *dout;
+  HIPCHK(ctx, hipMalloc(&ditems, (size_t)n * 20));
+  HIPCHK(ctx, hipMalloc(&dout, (size_t)n * 16));
+  HIPCHK(ctx, hipMemcpy(ditems, items, (size_t)n * 20, hipMemcpyHostToDevice));
+  HIPCHK(ctx, launch_test_filter_keys(ditems, n, len, dout, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpy(ab, dout, (size_t)n * 16, hipMemcpyDeviceToHost));
+  (void)hipFree(ditems);
+  (void)hipFree(dout);
+  return KH_OK;
+}
+
+int kh_tblk_check(kh_ctx *ctx, const uint8_t *items, uint32_t n, uint8_t *out) {
+  if (!ctx || !items || !out || !n) return KH_E_ARG;
+  if (ctx->vanity || !ctx->d_tblk || !ctx->tblocks) return KH_E_STATE;
+  (void)hipSetDevice(ctx->device);
+  uint8_t *ditems;
+  uint32_t *dout;
+  HIPCHK(ctx, hipMalloc(&ditems, (size_t)n * 20));
+  HIPCHK(ctx, hipMalloc(&dout, (size_t)n * 4));
+  HIPCHK(ctx, hipMemcpy(ditems, items, (size_t)n * 20, hipMemcpyHostToDevice));
+  HIPCHK(ctx, launch_test_tblk(ditems, n, ctx->d_tblk, ctx->tblocks, dout, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<uint32_t> ho(n);
+  HIPCHK(ctx, hipMemcpy(ho.data(), dout, (size_t)n * 4, hipMemcpyDeviceToHost));
+  (void)hipFree(ditems);
+  (void)hipFree(dout);
+  for (uint32_t i = 0; i < n; i++) out[i] = (uint8_t)ho[i];
+  return KH_OK;
+}
+
+int kh_scan_device_hits(kh_ctx *ctx, uint32_t *device_hits, uint32_t *redos) {
+  if (!ctx || !device_hits || !redos) return KH_E_ARG;
+  *device_hits = ctx->scan_dev_hits;
+  *redos = ctx->scan_redos;
+  return KH_OK;
+}
+
+int kh_bloom_check(kh_ctx *ctx, uint32_t layer, const uint8_t *items, uint32_t n, uint32_t len, uint8_t *out) {
+  return kh_bloom_check2(ctx, layer, items, n, len, out, nullptr);
+}
+
+int kh_bloom_check2(kh_ctx *ctx, uint32_t layer, const uint8_t *items, uint32_t n, uint32_t len, uint8_t *out,
+                    uint8_t *out_lazy) {
+  if (!ctx || !items || !out || !n || layer > 3) return KH_E_ARG;
+  // a prefix length (1..19) keys the target bloom only (vanity); the BSGS layers hold 32-byte X's or 20
+  if (len != 20 && len != 32 && !(layer == 0 && len >= 1 && len < 20)) return KH_E_ARG;
+  (void)hipSetDevice(ctx->device);
+  const size_t item_bytes = len == 32 ? 32 : 20;
   const uint8_t *bl;
   bloom_desc d;
   if (layer == 0) {
@@ -2856,18 +2939,26 @@ int kh_bloom_check(kh_ctx *ctx, uint32_t layer, const uint8_t *items, uint32_t n
     d = ctx->bd[layer - 1];
   }
   uint8_t *ditems;
-  uint32_t *dout;
-  HIPCHK(ctx, hipMalloc(&ditems, (size_t)n * len));
-  HIPCHK(ctx, hipMalloc(&dout, (size_t)n * 4));
-  HIPCHK(ctx, hipMemcpy(ditems, items, (size_t)n * len, hipMemcpyHostToDevice));
+  uint32_t *dout;  // n eager answers, then n lazy ones
+  HIPCHK(ctx, hipMalloc(&ditems, (size_t)n * item_bytes));
+  HIPCHK(ctx, hipMalloc(&dout, (size_t)n * 8));
+  HIPCHK(ctx, hipMemcpy(ditems, items, (size_t)n * item_bytes, hipMemcpyHostToDevice));
   uint32_t blocked = (layer == 1 && ctx->info.layer1_layout == KH_LAYER1_BLOCKED) ? 1 : 0;
-  HIPCHK(ctx, launch_test_bloom(ditems, n, len, bl, d, layer ? 1 : 0, blocked, dout, ctx->stream));
+  if (blocked && len != 32) {  // the blocked layer reads X[8..24)
+    (void)hipFree(ditems);
+    (void)hipFree(dout);
+    return KH_E_ARG;
+  }
+  HIPCHK(ctx, launch_test_bloom(ditems, n, len, bl, d, layer ? 1 : 0, blocked, dout, out_lazy ? dout + n : nullptr,
+                                ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  std::vector<uint32_t> ho(n);
-  HIPCHK(ctx, hipMemcpy(ho.data(), dout, (size_t)n * 4, hipMemcpyDeviceToHost));
+  std::vector<uint32_t> ho((size_t)n * 2, 0);
+  HIPCHK(ctx, hipMemcpy(ho.data(), dout, (size_t)n * (out_lazy ? 8 : 4), hipMemcpyDeviceToHost));
   (void)hipFree(ditems);
   (void)hipFree(dout);
   for (uint32_t i = 0; i < n; i++) out[i] = (uint8_t)ho[i];
+  if (out_lazy)
+    for (uint32_t i = 0; i < n; i++) out_lazy[i] = (uint8_t)ho[(size_t)n + i];
   return KH_OK;
 }
 

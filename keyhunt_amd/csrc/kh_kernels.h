@@ -289,5 +289,12 @@ hipError_t launch_setup(const setup_args &A, hipStream_t st);
 hipError_t launch_test_hash160(const uint32_t *xs, const uint32_t *ys, uint32_t n, uint32_t *out, hipStream_t st);
 hipError_t launch_test_field(const uint32_t *a, const uint32_t *b, uint32_t n, uint32_t *out, hipStream_t st);
 hipError_t launch_test_bloom(const uint8_t *items, uint32_t n, uint32_t len, const uint8_t *bloom,
-                             const bloom_desc &bd, uint32_t sharded, uint32_t blocked, uint32_t *out, hipStream_t st);
+                             const bloom_desc &bd, uint32_t sharded, uint32_t blocked, uint32_t *out, uint32_t *out_lazy,
+                             hipStream_t st);
+// probe-path parity kernels: hash160_comp2 / hash160_uncomp / eth_address per point (20 words), the
+// filter key pair (a, b) of a digest's first len bytes, tblk_probe against the blocked target filter
+hipError_t launch_test_digests(const uint32_t *xs, const uint32_t *ys, uint32_t n, uint32_t *out, hipStream_t st);
+hipError_t launch_test_filter_keys(const uint8_t *items, uint32_t n, uint32_t len, uint64_t *out, hipStream_t st);
+hipError_t launch_test_tblk(const uint8_t *items, uint32_t n, const uint4 *tblk, uint32_t tblocks, uint32_t *out,
+                            hipStream_t st);
 }  // namespace kh

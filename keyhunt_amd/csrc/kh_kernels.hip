@@ -1227,13 +1227,84 @@ __global__ void k_test_field(const uint32_t *a, const uint32_t *b, uint32_t n, u
   for (int k = 0; k < 8; k++) o[32 + k] = q.d[k];
 }
 
-// bloom_check of n items of `len` bytes (20 or 32); shard = first byte when sharded.
-__global__ void k_test_bloom(const uint8_t *items, uint32_t n, uint32_t len, const uint8_t *bloom, bloom_desc bd,
-                             uint32_t sharded, uint32_t blocked, uint32_t *out) {
+// the 20 bytes at p as 5 little-endian u32 words (a digest as the walks hold it)
+__device__ __forceinline__ void load_w5(uint32_t w[5], const uint8_t *p) {
+  for (int k = 0; k < 5; k++)
+    w[k] = (uint32_t)p[4 * k] | ((uint32_t)p[4 * k + 1] << 8) | ((uint32_t)p[4 * k + 2] << 16) |
+           ((uint32_t)p[4 * k + 3] << 24);
+}
+
+// The digests of the production forms, per point: hash160_comp2's two outputs (the interleaved pair
+// every compressed walk computes), hash160_uncomp, eth_address -> 20 words.
+__global__ void k_test_digests(const uint32_t *xs, const uint32_t *ys, uint32_t n, uint32_t *out) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const uint8_t *p = items + (size_t)i * len;
+  fe x, y;
+  load_fe(x, xs + (size_t)i * 8);
+  load_fe(y, ys + (size_t)i * 8);
+  uint32_t *o = out + (size_t)i * 20;
+  hash160_comp2(x, o, o + 5);
+  hash160_uncomp(x, y, o + 10);
+  eth_address(x, y, o + 15);
+}
+
+// The filter key pair (a, b) of the first `len` (1..20) bytes of n 20-byte items, as probe_h160
+// derives it: xxh64_20 for the whole digest, xxh64_prefix for a vanity prefix.
+__global__ void k_test_filter_keys(const uint8_t *items, uint32_t n, uint32_t len, uint64_t *out) {
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t w[5];
+  load_w5(w, items + (size_t)i * 20);
   uint64_t a, b;
+  if (len == 20) {
+    a = xxh64_20(w, KH_BLOOM_SEED);
+    b = xxh64_20(w, a);
+  } else {
+    a = xxh64_prefix(w, len, KH_BLOOM_SEED);
+    b = xxh64_prefix(w, len, a);
+  }
+  out[2 * (size_t)i] = a;
+  out[2 * (size_t)i + 1] = b;
+}
+
+// tblk_probe (the exact-target walks' probe) of n 20-byte items against the blocked target filter
+__global__ void k_test_tblk(const uint8_t *items, uint32_t n, const uint4 *tblk, uint32_t tblocks, uint32_t *out) {
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  walk_args A;
+  A.tblk = tblk;
+  A.tblocks = tblocks;
+  uint32_t w[5];
+  load_w5(w, items + (size_t)i * 20);
+  out[i] = tblk_probe(A, w) ? 1u : 0u;
+}
+
+// bloom_check of n items of `len` bytes; shard = first byte when sharded.  len 32: 32-byte items; len
+// 1..20 (20-byte items, unsharded only): the filter keyed on the first len bytes, as a vanity walk
+// probes it.  out_lazy (optional): the same answer from the walks' own early-exit probe, probe_h160
+// (bloom_probe_lazy) for 20-byte items and the BSGS walk's bloom_probe_lazy call for 32-byte ones.
+__global__ void k_test_bloom(const uint8_t *items, uint32_t n, uint32_t len, const uint8_t *bloom, bloom_desc bd,
+                             uint32_t sharded, uint32_t blocked, uint32_t *out, uint32_t *out_lazy) {
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t *p = items + (size_t)i * (len == 32 ? 32 : 20);
+  uint64_t a, b;
+  if (len < 20) {
+    uint32_t w[5];
+    load_w5(w, p);
+    a = xxh64_prefix(w, len, KH_BLOOM_SEED);
+    b = xxh64_prefix(w, len, a);
+    out[i] = bloom_probe(bloom, bd, a, b) ? 1u : 0u;
+    if (out_lazy) {
+      walk_args A;
+      A.tblk = nullptr;
+      A.bloom = bloom;
+      A.bd = bd;
+      A.probe_len = len;
+      out_lazy[i] = probe_h160(A, w) ? 1u : 0u;
+    }
+    return;
+  }
   if (len == 32) {
     uint64_t in[4];
     for (int k = 0; k < 4; k++) {
@@ -1259,9 +1330,29 @@ __global__ void k_test_bloom(const uint8_t *items, uint32_t n, uint32_t len, con
       w[k] = ((uint32_t)p[8 + 4 * k] << 24) | ((uint32_t)p[9 + 4 * k] << 16) | ((uint32_t)p[10 + 4 * k] << 8) |
              p[11 + 4 * k];
     out[i] = blk_match(reinterpret_cast<const uint4 *>(bf)[blk_index(w[0], bd)], w[1], w[2], w[3]) ? 1u : 0u;
+    if (out_lazy) out_lazy[i] = out[i];  // one probe form only
     return;
   }
   out[i] = bloom_probe(bf, bd, a, b) ? 1u : 0u;
+  if (!out_lazy) return;
+  if (len == 32) {
+    uint64_t in[4];
+    for (int k = 0; k < 4; k++) {
+      uint64_t v = 0;
+      for (int q = 7; q >= 0; q--) v = (v << 8) | p[8 * k + q];
+      in[k] = v;
+    }
+    out_lazy[i] = bloom_probe_lazy(bf, bd, a, [&](uint64_t s) { return xxh64_32(in, s); }) ? 1u : 0u;
+  } else {
+    walk_args A;
+    A.tblk = nullptr;
+    A.bloom = bf;
+    A.bd = bd;
+    A.probe_len = 20;
+    uint32_t w[5];
+    load_w5(w, p);
+    out_lazy[i] = probe_h160(A, w) ? 1u : 0u;
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1376,9 +1467,26 @@ hipError_t launch_test_field(const uint32_t *a, const uint32_t *b, uint32_t n, u
 }
 
 hipError_t launch_test_bloom(const uint8_t *items, uint32_t n, uint32_t len, const uint8_t *bloom,
-                             const bloom_desc &bd, uint32_t sharded, uint32_t blocked, uint32_t *out, hipStream_t st) {
+                             const bloom_desc &bd, uint32_t sharded, uint32_t blocked, uint32_t *out, uint32_t *out_lazy,
+                             hipStream_t st) {
   hipLaunchKernelGGL(k_test_bloom, dim3((n + 127) / 128), dim3(128), 0, st, items, n, len, bloom, bd, sharded, blocked,
-                     out);
+                     out, out_lazy);
+  return hipGetLastError();
+}
+
+hipError_t launch_test_digests(const uint32_t *xs, const uint32_t *ys, uint32_t n, uint32_t *out, hipStream_t st) {
+  hipLaunchKernelGGL(k_test_digests, dim3((n + 127) / 128), dim3(128), 0, st, xs, ys, n, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_test_filter_keys(const uint8_t *items, uint32_t n, uint32_t len, uint64_t *out, hipStream_t st) {
+  hipLaunchKernelGGL(k_test_filter_keys, dim3((n + 127) / 128), dim3(128), 0, st, items, n, len, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_test_tblk(const uint8_t *items, uint32_t n, const uint4 *tblk, uint32_t tblocks, uint32_t *out,
+                            hipStream_t st) {
+  hipLaunchKernelGGL(k_test_tblk, dim3((n + 127) / 128), dim3(128), 0, st, items, n, tblk, tblocks, out);
   return hipGetLastError();
 }
 

@@ -113,6 +113,11 @@ def lib() -> ctypes.CDLL:
     L.kh_hash160.argtypes = [P, u8p, ctypes.c_uint32, u8p]
     L.kh_field_ops.argtypes = [P, u8p, u8p, ctypes.c_uint32, u8p]
     L.kh_bloom_check.argtypes = [P, ctypes.c_uint32, u8p, ctypes.c_uint32, ctypes.c_uint32, u8p]
+    L.kh_bloom_check2.argtypes = [P, ctypes.c_uint32, u8p, ctypes.c_uint32, ctypes.c_uint32, u8p, u8p]
+    L.kh_digests.argtypes = [P, u8p, ctypes.c_uint32, u8p]
+    L.kh_filter_keys.argtypes = [P, u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]
+    L.kh_tblk_check.argtypes = [P, u8p, ctypes.c_uint32, u8p]
+    L.kh_scan_device_hits.argtypes = [P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
     L.kh_get_bloom.argtypes = [P, ctypes.c_uint32, u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
     L.kh_get_bsgs_table.argtypes = [P, u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
     L.kh_bsgs_set_table.argtypes = [P, u8p, ctypes.c_uint64]
@@ -362,6 +367,46 @@ class Engine:
         out = ctypes.create_string_buffer(len(items))
         self._chk(lib().kh_bloom_check(self._ctx, layer, b"".join(items), len(items), ln, out), "kh_bloom_check")
         return [b != 0 for b in out.raw]
+
+    def bloom_check2(self, layer: int, items: list[bytes], probe_len: int = 0) -> tuple[list[bool], list[bool]]:
+        """(eager, lazy) answers of the device's two probe forms (kh_bloom_check2).  probe_len 1..19
+        (layer 0, 20-byte items): the filter keyed on the items' first probe_len bytes."""
+        ln = probe_len or len(items[0])
+        assert all(len(it) == len(items[0]) for it in items) and (not probe_len or len(items[0]) == 20)
+        eager = ctypes.create_string_buffer(len(items))
+        lazy = ctypes.create_string_buffer(len(items))
+        self._chk(lib().kh_bloom_check2(self._ctx, layer, b"".join(items), len(items), ln, eager, lazy),
+                  "kh_bloom_check2")
+        return [b != 0 for b in eager.raw], [b != 0 for b in lazy.raw]
+
+    def digests(self, points: list[tuple[int, int]]) -> list[tuple[bytes, bytes, bytes, bytes]]:
+        """Per (x, y): hash160(02||X), hash160(03||X) (the walks' interleaved pair form), hash160(04||X||Y)
+        and the Ethereum address (kh_digests)."""
+        buf = b"".join(be32(x) + be32(y) for x, y in points)
+        out = ctypes.create_string_buffer(80 * len(points))
+        self._chk(lib().kh_digests(self._ctx, buf, len(points), out), "kh_digests")
+        raw = out.raw
+        return [tuple(raw[80 * i + 20 * k:80 * i + 20 * k + 20] for k in range(4)) for i in range(len(points))]
+
+    def filter_keys(self, items: list[bytes], length: int) -> list[tuple[int, int]]:
+        """Per 20-byte item the filter key pair (a, b) of its first `length` bytes (kh_filter_keys)."""
+        assert all(len(it) == 20 for it in items)
+        out = (ctypes.c_uint64 * (2 * len(items)))()
+        self._chk(lib().kh_filter_keys(self._ctx, b"".join(items), len(items), length, out), "kh_filter_keys")
+        return [(out[2 * i], out[2 * i + 1]) for i in range(len(items))]
+
+    def tblk_check(self, items: list[bytes]) -> list[bool]:
+        """The walks' probe of 20-byte items against the blocked exact-target filter (kh_tblk_check)."""
+        assert all(len(it) == 20 for it in items)
+        out = ctypes.create_string_buffer(len(items))
+        self._chk(lib().kh_tblk_check(self._ctx, b"".join(items), len(items), out), "kh_tblk_check")
+        return [b != 0 for b in out.raw]
+
+    def scan_device_hits(self) -> tuple[int, int]:
+        """(filter hits the device reported in the last scan, times that scan redid its chunk)."""
+        n, redos = ctypes.c_uint32(), ctypes.c_uint32()
+        self._chk(lib().kh_scan_device_hits(self._ctx, ctypes.byref(n), ctypes.byref(redos)), "kh_scan_device_hits")
+        return n.value, redos.value
 
     def get_bloom(self, layer: int) -> bytes:
         nb = ctypes.c_uint64()

@@ -5,7 +5,7 @@ TEST INFRASTRUCTURE.  Runs in the development container only (needs /root/refere
 
   tests/golden/ref_vectors.json  primitive vectors printed by oracle/_ref/ref_golden (field ops,
                                  pubkeys, hash160 02/03/04, XXH64, bloom sizing/fill, group
-                                 walk, BSGS baby tables at small M)
+                                 walk, BSGS baby tables at small M, XXH64 at every length 0..32)
   tests/golden/ref_e2e.json      end-to-end hit sets of oracle/_ref/keyhunt (the reference CLI) on
                                  known-answer windows, parsed from the
                                  KEYFOUNDKEYFOUND.txt it writes.

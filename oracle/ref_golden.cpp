@@ -269,6 +269,29 @@ int main() {
     printf("  {\"k\":\"%s\",\"xy\":\"%s\",\"keccak\":\"%s\",\"address\":\"%s\"}%s\n", ihex(k).c_str(),
            hexs(xy, 64).c_str(), hexs(d, 32).c_str(), hexs(d + 12, 20).c_str(), i == 39 ? "" : ",");
   }
+  printf("],\n");
+  // ---------------- XXH64 at every length 0..32 (the vanity bloom hashes hash160 prefixes) ----------------
+  // Emitted last and from a random stream of its own, so every key above stays byte-identical.
+  // Per length: two random buffers, all zeros, all 0xFF.
+  printf("\"xxh64_lengths\": [\n");
+  {
+    uint64_t st = 0x78786836346c656eULL;
+    auto rnd = [&st]() {  // splitmix64
+      uint64_t z = (st += 0x9E3779B97F4A7C15ULL);
+      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+      z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+      return z ^ (z >> 31);
+    };
+    for (int len = 0; len <= 32; len++)
+      for (int t = 0; t < 4; t++) {
+        uint8_t buf[32];
+        for (int i = 0; i < 32; i++) buf[i] = t < 2 ? (uint8_t)rnd() : t == 2 ? 0x00 : 0xFF;
+        uint64_t a = XXH64(buf, len, 0x59f2815b16f81798ULL);
+        uint64_t b = XXH64(buf, len, a);
+        printf("  {\"len\":%d,\"buf\":\"%s\",\"a\":\"%016llx\",\"b\":\"%016llx\"}%s\n", len, hexs(buf, len).c_str(),
+               (unsigned long long)a, (unsigned long long)b, len == 32 && t == 3 ? "" : ",");
+      }
+  }
   printf("]\n}\n");
   return 0;
 }

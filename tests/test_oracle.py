@@ -205,6 +205,18 @@ def test_oracle_second_masks_window(oracle):
     assert oracle.bsgs_second_masks(t, [0], q) == [0]
 
 
+def blk_spec_bits(xb, blocks):
+    """The blocked layer 1's layout, from its specification: (byte offset, bit) of the 16 bits the
+    32-byte X `xb` owns in a filter of 256 shards x `blocks` 16-byte blocks."""
+    base = xb[0] * blocks * 16 + ((int.from_bytes(xb[8:12], "big") * blocks) >> 32) * 16
+    s = [int.from_bytes(xb[12 + 4 * q:16 + 4 * q], "big") for q in range(2)]
+    for w in range(4):
+        a = s[w // 2] >> (8 * (w % 2))
+        for v in (a, a >> 4):
+            for f in (v & 15, 16 + ((v >> 16) & 15)):
+                yield base + 4 * w + (f >> 3), 1 << (f & 7)
+
+
 def test_oracle_blocked_layer1_check_vs_spec_model(oracle):
     """or_blk_check (the oracle's probe of the engine's blocked layer 1) against a filter written
     from the layout's specification in Python (the same model test_blocked_layer1_bytes_match_
@@ -216,13 +228,7 @@ def test_oracle_blocked_layer1_check_vs_spec_model(oracle):
     model = bytearray(256 * blocks * 16)
 
     def words(xb):
-        base = xb[0] * blocks * 16 + ((int.from_bytes(xb[8:12], "big") * blocks) >> 32) * 16
-        s = [int.from_bytes(xb[12 + 4 * q:16 + 4 * q], "big") for q in range(2)]
-        for w in range(4):
-            a = s[w // 2] >> (8 * (w % 2))
-            for v in (a, a >> 4):
-                for f in (v & 15, 16 + ((v >> 16) & 15)):
-                    yield base + 4 * w + (f >> 3), 1 << (f & 7)
+        return blk_spec_bits(xb, blocks)
 
     ins = [rng.getrandbits(256).to_bytes(32, "big") for _ in range(3000)]
     for xb in ins:
