@@ -9,6 +9,7 @@
  *                          searchbinary 3065-3089, parity fix-up 3619-3636)
  *   kh_set_targets     <- readFileAddress/forceReadFileAddress/...XPoint  keyhunt.cpp:7239-7490
  *                         + initBloomFilter 7605-7626 + _sort 1359-1364
+ *   kh_minikeys_scan   <- thread_process_minikeys, one chunk of N valid minikeys  keyhunt.cpp:3184-3255
  *   kh_bsgs_setup      <- BSGS parameter block                            keyhunt.cpp:1454-1842
  *   kh_bsgs_build      <- thread_bPload / thread_bPload_2blooms + bsgs_sort keyhunt.cpp:5284-5644, 2466-2503
  *   kh_bsgs_scan       <- thread_process_bsgs (sequential), bases of 2N   keyhunt.cpp:4549-4888
@@ -165,6 +166,44 @@ int kh_scan_memory(uint64_t n_keys, uint32_t mode, uint32_t search, uint64_t *ne
  * KH_MODE_ETH (-m rmd160 -c eth), exact targets. */
 int kh_set_rmd_batch(kh_ctx *ctx, uint32_t group);
 
+/* ---- minikeys ----------------------------------------------------------------------------- */
+/* -m minikeys (thread_process_minikeys, keyhunt.cpp:3094-3259).  A minikey is 'S' plus 21 characters of a
+ * 58-character alphabet (Ccoinbuffer, -8), held as 21 raw digits 0..57, most significant first.  From a
+ * base the worker walks candidates base+1, base+2, ... on that base-58 odometer (the top digit wraps to
+ * all zeros), 4 at a time; a candidate is VALID when SHA-256(22 characters || '?') starts with a zero
+ * byte; a valid candidate's key is SHA-256(22 characters) read big-endian, and hash160(04||X||Y) of
+ * key*G is looked up in the targets of kh_set_targets / kh_targets_load. */
+#define KH_MINIKEY_ALPHABET "123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz"
+typedef struct {
+  uint8_t key[32];      /* SHA-256(minikey) as the reference prints it: not reduced mod n */
+  uint64_t offset;      /* candidate number, 1-based from the base */
+  uint32_t ordinal;     /* 0-based index among the call's valid candidates */
+  char minikey[24];     /* the 22 characters, NUL-terminated */
+} kh_minikey_hit;
+/* -8: the 58 characters (NULL = KH_MINIKEY_ALPHABET) */
+int kh_minikeys_set_alphabet(kh_ctx *ctx, const char alphabet[58]);
+/* candidates per filter launch (rounded up to a multiple of 4, at most 2^28) and the device queue's
+ * initial size in valid candidates; 0 = automatic (windows that shrink towards the stopping point, a
+ * queue of 1/200 of the window).  A queue too small for a window's valid candidates is grown and the
+ * window done again. */
+int kh_minikeys_set_window(kh_ctx *ctx, uint64_t candidates_per_launch, uint32_t queue_entries);
+/* One chunk of one reference thread: walk the groups of 4 candidates from base until at least need_valid
+ * valid ones have been seen.  *n_candidates = the candidates walked (a multiple of 4), *n_valid = the
+ * valid ones among them (need_valid .. need_valid + 3), every one of which is checked against the
+ * targets.  hits: the confirmed ones in candidate order; those with ordinal >= need_valid belong to the
+ * group the reference carries into its next chunk, where it processes them first.  Work past the
+ * stopping point -- the rest of the last launch window -- is discarded. */
+int kh_minikeys_scan(kh_ctx *ctx, const uint8_t base[21], uint64_t need_valid, kh_minikey_hit *hits, uint32_t cap,
+                     uint32_t *n_hits, uint64_t *n_candidates, uint64_t *n_valid);
+/* parity hooks: the valid candidates among base+1 .. base+n_candidates (ascending, 1-based), from the
+ * filter kernel; per given candidate offset key[32] | hash160(04||X||Y)[20], from the key kernel (a key
+ * that is 0 mod n leaves its hash160 zero); the device queue's size and how often the last scan / valid
+ * call grew it and redid a window */
+int kh_minikeys_valid(kh_ctx *ctx, const uint8_t base[21], uint64_t n_candidates, uint64_t *offsets, uint64_t cap,
+                      uint64_t *n);
+int kh_minikeys_keys(kh_ctx *ctx, const uint8_t base[21], const uint64_t *offsets, uint32_t n, uint8_t *out52);
+int kh_minikeys_queue(kh_ctx *ctx, uint32_t *entries, uint32_t *redos);
+
 /* ---- BSGS --------------------------------------------------------------------------------- */
 /* layer-1 layout for the next kh_bsgs_setup (KH_LAYER1_BLOCKED unless changed) */
 int kh_bsgs_set_layer1(kh_ctx *ctx, uint32_t layout);
@@ -224,7 +263,8 @@ int kh_bsgs_refine_stats(kh_ctx *ctx, uint64_t *first_level, uint64_t *second_le
 /* ---- measurement -------------------------------------------------------------------------- */
 /* Accumulated device time of walk launches of one kind since the last reset, measured with
  * HIP events on the context's stream.  kind: 0 address/rmd160, 1 xpoint, 2 bsgs giant,
- * 3 bsgs build, 4 lane setup (scalar mult). */
+ * 3 bsgs build, 4 lane setup (scalar mult), 5 minikeys filter (points = candidates), 6 minikeys keys
+ * (points = valid candidates). */
 int kh_kernel_time(kh_ctx *ctx, uint32_t kind, uint64_t *launches, double *ms, uint64_t *points);
 int kh_kernel_time_reset(kh_ctx *ctx);
 

@@ -272,7 +272,47 @@ struct refine_args {
   kh::bloom_desc bd2;
 };
 
+// -m minikeys (thread_process_minikeys, keyhunt.cpp:3094-3259).  A minikey is 'S' plus 21 characters
+// of a 58-character alphabet, held as 21 raw digits (most significant first); candidate c (1-based)
+// of a chunk is base + c on that base-58 odometer, wrapping to all zeros past the top digit.
+// A ROW is the 58 candidates that share their upper 20 digits: row r (relative to the base's own
+// row) holds candidates c = 58 r + j - base[20], j < 58.
+#define KH_MINI_STAGE 256  // k_mini_filter: valid candidates a block stages in LDS before its one queue atomic
+#define KH_MINI_BATCH 8    // k_mini_keys: keys per lane that share one field inversion
+struct mini_base {
+  uint32_t digit[21];  // raw digits 0..57
+  uint32_t alpha[58];  // the alphabet's characters
+};
+// k_mini_filter: one row per lane; candidates of the window (win_start, win_start + win_n] whose
+// SHA-256(22 characters || '?') starts with a zero byte go to the queue as absolute offsets c
+struct mini_filter_args {
+  mini_base b;
+  uint64_t row0;       // the window's first row
+  uint32_t rows;       // lanes
+  uint64_t win_start, win_n;
+  uint32_t *count;     // queue head: counts every valid candidate, also those past cap
+  uint64_t *queue;
+  uint32_t cap;
+};
+// k_mini_keys: KH_MINI_BATCH queue entries per lane: key = SHA-256(22 characters), P = key*G (comb),
+// one inversion per lane for its batch, hash160(04||X||Y), blocked target filter, device hit (idx = c)
+struct mini_keys_args {
+  mini_base b;
+  const uint64_t *queue;
+  uint32_t n;          // entries
+  uint64_t limit;      // entries with c > limit are skipped (work past the chunk's stopping point)
+  const uint32_t *comb;
+  const uint4 *tblk;   // null: no probe (parity hook)
+  uint32_t tblocks;
+  uint32_t *hit_count;
+  kh_dev_hit *hits;
+  uint32_t hit_cap;
+  uint32_t *out13;     // parity hook (or null): per entry the key's 8 words and the hash160's 5, as bytes in memory
+};
+
 namespace kh {
+hipError_t launch_mini_filter(const mini_filter_args &A, hipStream_t st);
+hipError_t launch_mini_keys(const mini_keys_args &A, hipStream_t st);
 hipError_t launch_walk(int mode, const walk_args &A, hipStream_t st, int H = KH_WALK_H);
 // Inversion-pad rows per lane the walk launch_walk runs for (mode, blocked target filter) touches: the
 // sparse-pad walks (k_walk's SPARSE: the BSGS giant walks, -m xpoint against the blocked filter) keep

@@ -192,9 +192,12 @@ __device__ __forceinline__ void x_bytes_u64(const fe &x, uint64_t in[4]) {
 // of the 20 bytes, the 16-byte block is (w0 * blocks) >> 32 and the bit positions come from w1, w2
 // (kh_blk_masks).  One 16-B load, no XXH64.  Every filter hit is still confirmed by the
 // host's exact table search (searchbinary), so the reported hits are the reference's.
+__device__ __forceinline__ bool tblk_probe_at(const uint4 *tblk, uint32_t tblocks, const uint32_t w[5]) {
+  const uint32_t blk = (uint32_t)(((uint64_t)w[0] * tblocks) >> 32);
+  return blk_match(tblk[blk], w[1], w[2], w[3]);
+}
 __device__ __forceinline__ bool tblk_probe(const walk_args &A, const uint32_t w[5]) {
-  const uint32_t blk = (uint32_t)(((uint64_t)w[0] * A.tblocks) >> 32);
-  return blk_match(A.tblk[blk], w[1], w[2], w[3]);
+  return tblk_probe_at(A.tblk, A.tblocks, w);
 }
 
 // one 20-byte hash into the target bloom: the whole hash (address/rmd160), or its first
@@ -1179,6 +1182,176 @@ __global__ void __launch_bounds__(64) k_refine(refine_args A) {
 }
 
 // ------------------------------------------------------------------------------------------
+// -m minikeys (thread_process_minikeys, keyhunt.cpp:3094-3259): a dense filter kernel (one-block
+// SHA-256 of 23 bytes per candidate, 1 in 256 passes) and a sparse key kernel (per valid candidate a
+// SHA-256 of 22 bytes, a scalar multiplication and a hash160), joined by a device queue.
+// ------------------------------------------------------------------------------------------
+namespace {
+// d[0..N) (most significant first) += v on the base-58 odometer; the carry out of d[0] is dropped,
+// which is increment_minikey_index's wrap to all zeros (keyhunt.cpp:6520-6536)
+template <int N>
+__device__ __forceinline__ void mini_add(uint32_t d[N], const uint32_t *base, uint64_t v) {
+#pragma unroll
+  for (int i = N - 1; i >= 0; i--) {
+    const uint64_t q = v / 58u;
+    uint32_t t = base[i] + (uint32_t)(v - q * 58u);
+    v = q;
+    if (t >= 58u) {
+      t -= 58u;
+      v += 1;
+    }
+    d[i] = t;
+  }
+}
+// message words 0..4 of 'S' || c[0..19): bytes 0..19 of the block
+__device__ __forceinline__ void mini_words(uint32_t w[16], const uint32_t c[21]) {
+  w[0] = (0x53u << 24) | (c[0] << 16) | (c[1] << 8) | c[2];
+#pragma unroll
+  for (int k = 1; k < 5; k++) w[k] = (c[4 * k - 1] << 24) | (c[4 * k] << 16) | (c[4 * k + 1] << 8) | c[4 * k + 2];
+#pragma unroll
+  for (int k = 6; k < 15; k++) w[k] = 0;
+}
+}  // namespace
+
+// One row per lane: the 58 candidates that differ in their last character only, so message words
+// 0..4 and byte 20 are fixed for the lane's whole run and the first rounds and schedule terms that
+// depend on them alone are loop invariants.  Valid candidates are staged in LDS and a block reserves
+// queue space with one device atomic (a block's 14848 candidates hold 58 valid ones on average).
+__global__ void __launch_bounds__(256) k_mini_filter(mini_filter_args A) {
+  __shared__ uint32_t s_alpha[64];
+  __shared__ uint32_t s_stage[KH_MINI_STAGE];
+  __shared__ uint32_t s_n, s_at;
+  if (threadIdx.x < 58) s_alpha[threadIdx.x] = A.b.alpha[threadIdx.x];
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g < A.rows) {
+    const uint64_t r = A.row0 + g;
+    uint32_t d[20], c[21];
+    mini_add<20>(d, A.b.digit, r);
+#pragma unroll
+    for (int i = 0; i < 20; i++) c[i] = s_alpha[d[i]];
+    uint32_t w0[16];
+    mini_words(w0, c);
+    const uint32_t w5 = (c[19] << 24) | 0x3F80u;  // c[19], the moving character, '?', the padding bit
+    // candidate number of the row's j = 0, minus win_start + 1: in the window iff (rel + j) < win_n
+    const uint64_t rel = r * 58u - A.b.digit[20] - A.win_start - 1;
+#pragma unroll 1
+    for (uint32_t j = 0; j < 58; j++) {
+      uint32_t w[16], st[8];
+#pragma unroll
+      for (int k = 0; k < 16; k++) w[k] = w0[k];
+      w[5] = w5 | (s_alpha[j] << 16);
+      w[15] = 23 * 8;
+      sha256_init(st);
+      sha256_transform(st, w);
+      if ((st[0] >> 24) == 0 && rel + j < A.win_n) {
+        const uint32_t lo = (uint32_t)(rel + j);  // offset - win_start - 1 (< 2^32: the host bounds win_n)
+        const uint32_t slot = atomicAdd(&s_n, 1u);
+        if (slot < KH_MINI_STAGE) {
+          s_stage[slot] = lo;
+        } else {  // more than the stage holds (never, in practice): straight to the queue
+          const uint32_t q = atomicAdd(A.count, 1u);
+          if (q < A.cap) A.queue[q] = A.win_start + 1 + lo;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const uint32_t n = min(s_n, (uint32_t)KH_MINI_STAGE);
+  if (threadIdx.x == 0 && n) s_at = atomicAdd(A.count, n);
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+    const uint32_t q = s_at + i;
+    if (q < A.cap) A.queue[q] = A.win_start + 1 + s_stage[i];
+  }
+}
+
+// KH_MINI_BATCH queue entries per lane.  Forward: rebuild the 22 characters, key = SHA-256 of them
+// (reduced mod n for the multiplication; a key = 0 mod n is skipped), P = key*G in Jacobian
+// coordinates, running product of the Z's.  One inversion, then backward: affine P, hash160, probe.
+__global__ void __launch_bounds__(64) k_mini_keys(mini_keys_args A) {
+  __shared__ uint32_t s_alpha[64];
+  if (threadIdx.x < 58) s_alpha[threadIdx.x] = A.b.alpha[threadIdx.x];
+  __syncthreads();
+  const uint32_t T = gridDim.x * blockDim.x;
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  fe px[KH_MINI_BATCH], py[KH_MINI_BATCH], pz[KH_MINI_BATCH], pre[KH_MINI_BATCH];
+  uint32_t live = 0;
+  fe acc;
+  fe_set_u32(acc, 1);
+#pragma unroll 1
+  for (uint32_t t = 0; t < KH_MINI_BATCH; t++) {
+    const uint64_t e = (uint64_t)t * T + g;
+    pre[t] = acc;
+    if (e >= A.n) continue;
+    const uint64_t off = A.queue[e];
+    if (off > A.limit) continue;
+    uint32_t d[21], c[21], w[16], st[8];
+    mini_add<21>(d, A.b.digit, off);
+#pragma unroll
+    for (int i = 0; i < 21; i++) c[i] = s_alpha[d[i]];
+    mini_words(w, c);
+    w[5] = (c[19] << 24) | (c[20] << 16) | 0x8000u;
+    w[15] = 22 * 8;
+    sha256_init(st);
+    sha256_transform(st, w);
+    if (A.out13) {
+#pragma unroll
+      for (int i = 0; i < 8; i++) A.out13[e * 13 + i] = bswap32(st[i]);
+    }
+    // the digest read big-endian (Set32Bytes) as 8 LE limbs, minus n when it is not below n
+    uint32_t s[8], u[8], bo = 0, nz = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) s[i] = st[7 - i];
+#pragma unroll
+    for (int i = 0; i < 8; i++) u[i] = subb(s[i], order_limb(i), bo, bo);
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      s[i] = bo ? s[i] : u[i];
+      nz |= s[i];
+    }
+    if (!nz) continue;
+    gej P;
+    comb_mult_jac(P, s, A.comb);
+    px[t] = P.x;
+    py[t] = P.y;
+    pz[t] = P.z;
+    fe_mul(acc, acc, P.z);
+    live |= 1u << t;
+  }
+  if (!live) return;
+  fe inv;
+  fe_inv(inv, acc);
+#pragma unroll 1
+  for (int t = KH_MINI_BATCH - 1; t >= 0; t--) {
+    if (!((live >> t) & 1u)) continue;
+    fe zi, zi2, zi3, x, y;
+    fe_mul(zi, inv, pre[t]);
+    fe_mul(inv, inv, pz[t]);
+    fe_sqr(zi2, zi);
+    fe_mul(zi3, zi2, zi);
+    fe_mul(x, px[t], zi2);
+    fe_mul(y, py[t], zi3);
+    uint32_t h[5];
+    hash160_uncomp(x, y, h);
+    const uint64_t e = (uint64_t)t * T + g;
+    if (A.out13) {
+#pragma unroll
+      for (int i = 0; i < 5; i++) A.out13[e * 13 + 8 + i] = h[i];
+    }
+    if (A.tblk && tblk_probe_at(A.tblk, A.tblocks, h)) {
+      const uint32_t slot = atomicAdd(A.hit_count, 1u);
+      if (slot < A.hit_cap) {
+        A.hits[slot].idx = A.queue[e];
+        A.hits[slot].kind = 2;
+        A.hits[slot].aux = 0;
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // Parity-test kernels (exercised by tests/ through the C-ABI): hash160 and bloom probes of
 // given inputs, field ops.
 // ------------------------------------------------------------------------------------------
@@ -1448,6 +1621,17 @@ hipError_t launch_walk_zinv(int mode, const walk_args &A, hipStream_t st) {
 
 hipError_t launch_refine(const refine_args &A, hipStream_t st) {
   hipLaunchKernelGGL(k_refine, dim3((A.cap + 63) / 64), dim3(64), 0, st, A);
+  return hipGetLastError();
+}
+
+hipError_t launch_mini_filter(const mini_filter_args &A, hipStream_t st) {
+  hipLaunchKernelGGL(k_mini_filter, dim3((A.rows + 255) / 256), dim3(256), 0, st, A);
+  return hipGetLastError();
+}
+
+hipError_t launch_mini_keys(const mini_keys_args &A, hipStream_t st) {
+  const uint32_t lanes = (A.n + KH_MINI_BATCH - 1) / KH_MINI_BATCH;
+  hipLaunchKernelGGL(k_mini_keys, dim3((lanes + 63) / 64), dim3(64), 0, st, A);
   return hipGetLastError();
 }
 

@@ -48,6 +48,15 @@ class KhBsgsFound(ctypes.Structure):
     _fields_ = [("target", ctypes.c_uint32), ("pad", ctypes.c_uint32), ("key", ctypes.c_uint8 * 32)]
 
 
+class KhMinikeyHit(ctypes.Structure):
+    _fields_ = [("key", ctypes.c_uint8 * 32), ("offset", ctypes.c_uint64), ("ordinal", ctypes.c_uint32),
+                ("minikey", ctypes.c_char * 24)]
+
+
+MINIKEY_ALPHABET = "123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz"
+TIME_MINI_FILTER, TIME_MINI_KEYS = 5, 6
+KH_E_STATE, KH_E_OVERFLOW = -4, -5
+
 _lib = None
 
 
@@ -121,6 +130,14 @@ def lib() -> ctypes.CDLL:
     L.kh_get_bloom.argtypes = [P, ctypes.c_uint32, u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
     L.kh_get_bsgs_table.argtypes = [P, u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
     L.kh_bsgs_set_table.argtypes = [P, u8p, ctypes.c_uint64]
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    L.kh_minikeys_set_alphabet.argtypes = [P, ctypes.c_char_p]
+    L.kh_minikeys_set_window.argtypes = [P, ctypes.c_uint64, ctypes.c_uint32]
+    L.kh_minikeys_scan.argtypes = [P, u8p, ctypes.c_uint64, ctypes.POINTER(KhMinikeyHit), ctypes.c_uint32,
+                                   ctypes.POINTER(ctypes.c_uint32), u64p, u64p]
+    L.kh_minikeys_valid.argtypes = [P, u8p, ctypes.c_uint64, u64p, ctypes.c_uint64, u64p]
+    L.kh_minikeys_keys.argtypes = [P, u8p, u64p, ctypes.c_uint32, u8p]
+    L.kh_minikeys_queue.argtypes = [P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
     _lib = L
     return L
 
@@ -141,6 +158,14 @@ class ScanHit:
     offset: int
     kind: int
     compressed: bool
+
+
+@dataclass
+class MinikeyHit:
+    key: int
+    offset: int
+    ordinal: int
+    minikey: str
 
 
 class Engine:
@@ -246,6 +271,62 @@ class Engine:
         r = lib().kh_scan(self._ctx, be32(start), be32(stride), n_keys, mode, search, hits, cap, ctypes.byref(n))
         return r, [ScanHit(int.from_bytes(bytes(h.key), "big"), h.offset, h.kind, bool(h.compressed))
                    for h in hits[: min(n.value, cap)]]
+
+    # -- minikeys ------------------------------------------------------------------------------
+    def minikeys_set_alphabet(self, alphabet: str | None = None) -> None:
+        """-8: the 58 characters raw digits map to (None = the default base-58 alphabet)."""
+        assert alphabet is None or len(alphabet) == 58
+        self._chk(lib().kh_minikeys_set_alphabet(self._ctx, alphabet.encode("latin-1") if alphabet else None),
+                  "kh_minikeys_set_alphabet")
+
+    def minikeys_set_window(self, candidates_per_launch: int = 0, queue_entries: int = 0) -> None:
+        """Candidates per filter launch and the device queue's initial size (0, 0 = automatic)."""
+        self._chk(lib().kh_minikeys_set_window(self._ctx, candidates_per_launch, queue_entries),
+                  "kh_minikeys_set_window")
+
+    def minikeys_scan_status(self, base: list[int], need_valid: int, cap: int = 4096):
+        """kh_minikeys_scan returning (status, hits, n_hits, n_candidates, n_valid) instead of raising."""
+        hits = (KhMinikeyHit * max(cap, 1))()
+        n, nc, nv = ctypes.c_uint32(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        r = lib().kh_minikeys_scan(self._ctx, bytes(base), need_valid, hits, cap, ctypes.byref(n), ctypes.byref(nc),
+                                   ctypes.byref(nv))
+        out = [MinikeyHit(int.from_bytes(bytes(h.key), "big"), h.offset, h.ordinal, h.minikey.decode("latin-1"))
+               for h in hits[: min(n.value, cap)]]
+        return r, out, n.value, nc.value, nv.value
+
+    def minikeys_scan(self, base: list[int], need_valid: int, cap: int = 4096):
+        """One chunk from `base` (21 raw digits): (hits in candidate order, candidates walked, valid ones)."""
+        r, out, _, nc, nv = self.minikeys_scan_status(base, need_valid, cap)
+        self._chk(r, "kh_minikeys_scan")
+        return out, nc, nv
+
+    def minikeys_valid(self, base: list[int], n_candidates: int) -> list[int]:
+        """The valid candidates among base+1 .. base+n_candidates, ascending (the filter kernel)."""
+        n = ctypes.c_uint64(0)
+        cap = n_candidates // 128 + 64
+        buf = (ctypes.c_uint64 * cap)()
+        r = lib().kh_minikeys_valid(self._ctx, bytes(base), n_candidates, buf, cap, ctypes.byref(n))
+        if r == KH_E_OVERFLOW:
+            cap = n.value
+            buf = (ctypes.c_uint64 * cap)()
+            r = lib().kh_minikeys_valid(self._ctx, bytes(base), n_candidates, buf, cap, ctypes.byref(n))
+        self._chk(r, "kh_minikeys_valid")
+        return list(buf[: n.value])
+
+    def minikeys_keys(self, base: list[int], offsets: list[int]) -> list[tuple[int, bytes]]:
+        """Per candidate offset (key, hash160(04||X||Y)) as the key kernel computes them."""
+        n = len(offsets)
+        out = ctypes.create_string_buffer(52 * n)
+        self._chk(lib().kh_minikeys_keys(self._ctx, bytes(base), (ctypes.c_uint64 * n)(*offsets), n, out),
+                  "kh_minikeys_keys")
+        raw = out.raw
+        return [(int.from_bytes(raw[52 * i:52 * i + 32], "big"), raw[52 * i + 32:52 * i + 52]) for i in range(n)]
+
+    def minikeys_queue(self) -> tuple[int, int]:
+        """(device queue entries, times the last minikeys call grew the queue and redid a window)."""
+        a, b = ctypes.c_uint32(), ctypes.c_uint32()
+        self._chk(lib().kh_minikeys_queue(self._ctx, ctypes.byref(a), ctypes.byref(b)), "kh_minikeys_queue")
+        return a.value, b.value
 
     # -- BSGS ----------------------------------------------------------------------------------
     def bsgs_setup(self, n: int, k: int, layer1: int = None) -> KhBsgsInfo:

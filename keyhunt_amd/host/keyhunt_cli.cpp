@@ -10,7 +10,8 @@
 // follow the reference's cursors (see take_bases).  -e (address/rmd160/xpoint), -c eth (address/rmd160)
 // -m vanity, and -S / -6 (the BSGS table files and the address/rmd160/xpoint data_<hex>.dat target
 // cache, in the reference's formats) and -B ggsb / --bsgs-block-count / --bsgs-block-size are
-// provided; minikeys are rejected.
+// provided.  Built with -DKH_WITH_MINIKEYS (bin/minikeys-amd) the same source also takes -m minikeys
+// with -C and -8 (thread_process_minikeys, keyhunt.cpp:3094-3259); bin/keyhunt-amd rejects that mode.
 #include <ctype.h>
 #include <fcntl.h>
 #include <getopt.h>
@@ -113,7 +114,8 @@ std::string rmd_to_address(const uint8_t h[20]) {
 // ---------------------------------------------------------------------------------------------
 // options and shared state
 // ---------------------------------------------------------------------------------------------
-enum { MODE_ADDRESS, MODE_RMD160, MODE_XPOINT, MODE_BSGS, MODE_VANITY };
+// MODE_MINIKEYS is a mode name of the build with KH_WITH_MINIKEYS only (bin/minikeys-amd)
+enum { MODE_ADDRESS, MODE_RMD160, MODE_XPOINT, MODE_BSGS, MODE_VANITY, MODE_MINIKEYS };
 struct options {
   int mode = MODE_ADDRESS;
   const char *file = nullptr;
@@ -158,6 +160,10 @@ struct options {
   int rmd_batch = 1024;  // --rmd-batch-size (keyhunt.cpp:301, 815-829), -m rmd160 only
   bool crypto_given = false;      // -c (FLAGCRYPTO set): no "Setting search for btc" line
   std::string range_start_str, range_end_str;  // -r as typed (BSGS prints them so, keyhunt.cpp:1529-1531)
+  // -m minikeys: -C (the base, 'S' + 21 characters) and -8 (the alphabet; NULL = the default)
+  bool have_minikey = false;
+  std::string minikey_str;
+  const char *alphabet = nullptr;
 } opt;
 // keyhunt.cpp:419; ggsb and angrygiant walk like sequential (ggsb with BSGS_STEP = 2 x block size)
 const char *BSGS_MODES[7] = {"sequential", "backward", "both", "random", "dance", "ggsb", "angrygiant"};
@@ -553,15 +559,15 @@ bool write_mapped_data_file(const std::string &path, const mapped::filter &F, co
   return ok;
 }
 
-void addr_worker(addr_job *j) {
+// a worker's context with the job's targets set (or read from / written to the -S cache)
+int open_with_targets(addr_job *j, kh_ctx **out) {
   kh_ctx *ctx = nullptr;
   int r = kh_open(j->device, &ctx);
   if (r) {
     fprintf(stderr, "[E] GPU %d: %s\n", j->device, kh_strerror(r));
-    j->rc = r;
-    g_running--;
-    return;
+    return r;
   }
+  *out = ctx;
   if (opt.mode == MODE_VANITY)
     r = kh_set_vanity(ctx, opt.vanity.ranges.data(), opt.vanity.ranges.size() / 40, (uint32_t)opt.vanity.min_bytes,
                       opt.vanity.total);
@@ -573,6 +579,143 @@ void addr_worker(addr_job *j) {
     printf("[D] size data %llu\n", (unsigned long long)(j->rows->size()));  // keyhunt.cpp:7773
     printf("[+] Writing file %s ........\n", j->data_file);
     r = kh_targets_save(ctx, j->data_file);
+  }
+  return r;
+}
+
+// -m minikeys (keyhunt.cpp:1293-1323, 3094-3259, 6502-6559).  The shared cursor is the raw base, 21
+// digits 0..57; a chunk takes it and advances it by 253 N candidates (increment_minikey_N: one valid
+// minikey in 256 candidates, so chunks overlap by about 3 N of them).
+uint8_t g_mk_raw[21];
+uint8_t g_mk_n[22];  // minikeyN: the base-58 digits of 253 N, filled from index 20 down
+int g_mk_limit = 0;  // minikey_n_limit: one more than their count
+void minikey_n_init(uint64_t nseq) {
+  memset(g_mk_n, 0, sizeof g_mk_n);  // the reference's malloc: the one digit read past those it sets is 0
+  unsigned __int128 aux = (unsigned __int128)nseq * 253;
+  int i = 20;
+  while (aux != 0 && i > 0) {
+    g_mk_n[i] = (uint8_t)(aux % 58);
+    aux /= 58;
+    i--;
+  }
+  g_mk_limit = 21 - i;
+}
+void increment_minikey_n(uint8_t raw[21]) {
+  int i = 20, k = 0;
+  while (i > 0 && k < g_mk_limit) {
+    raw[i] = (uint8_t)(raw[i] + g_mk_n[i]);
+    if (raw[i] > 57) {
+      raw[i] = raw[i] % 58;
+      raw[i - 1]++;
+    }
+    i--;
+    k++;
+  }
+  // the last carry can leave a digit at 58, which indexes the reference's alphabet at its terminator;
+  // here it is carried upward (and out of the top digit, as the odometer wraps)
+  for (i = 20; i > 0; i--)
+    if (raw[i] > 57) {
+      raw[i] = (uint8_t)(raw[i] - 58);
+      raw[i - 1]++;
+    }
+  raw[0] %= 58;
+}
+
+void write_minikey(kh_ctx *ctx, const kh_minikey_hit &h) {
+  // keyhunt.cpp:3226-3241: the key through GetBase16 (no leading zeros)
+  uint8_t xy[64];
+  kh_pubkeys(ctx, h.key, 1, xy);
+  fe x, y;
+  fe_from_be(x, xy);
+  fe_from_be(y, xy + 32);
+  uint32_t hw[5];
+  hash160_uncomp(x, y, hw);
+  uint8_t rmd[20], pfx = 4;
+  memcpy(rmd, hw, 20);
+  const std::string pub = hex(&pfx, 1) + hex(xy, 64), addr = rmd_to_address(rmd), k = u_hex(u_from_be32(h.key));
+  std::lock_guard<std::mutex> lk(g_keys_mtx);
+  FILE *f = fopen("KEYFOUNDKEYFOUND.txt", "a+");
+  if (f) {
+    fprintf(f, "Private Key: %s\npubkey: %s\nminikey: %s\naddress: %s\n", k.c_str(), pub.c_str(), h.minikey, addr.c_str());
+    fclose(f);
+  }
+  printf("\nHIT!! Private Key: %s\npubkey: %s\nminikey: %s\naddress: %s\n", k.c_str(), pub.c_str(), h.minikey,
+         addr.c_str());
+  fflush(stdout);
+}
+
+void mini_worker(addr_job *j) {
+  kh_ctx *ctx = nullptr;
+  int r = open_with_targets(j, &ctx);
+  if (!ctx) {
+    j->rc = r;
+    g_running--;
+    return;
+  }
+  if (!r && opt.alphabet) r = kh_minikeys_set_alphabet(ctx, opt.alphabet);
+  if (r) fprintf(stderr, "[E] GPU %d: %s (%s)\n", j->device, kh_strerror(r), kh_last_error(ctx));
+  const char *alpha = opt.alphabet ? opt.alphabet : B58;
+  std::vector<kh_minikey_hit> hits(1 << 12), carried;
+  uint64_t carry = 0;  // valid minikeys of the previous chunk's last group of 4 (count_valid, 3187-3210)
+  std::random_device rd;
+  while (!r) {
+    uint8_t base[21];
+    {
+      std::lock_guard<std::mutex> lk(g_cursor_mtx);
+      if (opt.random) {  // counter.Rand(256), each byte % 58 (3122-3127)
+        for (int k = 0; k < 21; k++) base[k] = (uint8_t)((rd() & 0xFF) % 58);
+      } else {
+        memcpy(base, g_mk_raw, 21);
+        increment_minikey_n(g_mk_raw);
+      }
+    }
+    char text[24] = {0};
+    text[0] = 'S';
+    for (int k = 0; k < 21; k++) text[1 + k] = alpha[base[k]];
+    text[22] = '?';
+    if (opt.matrix) {
+      printf("[+] Base minikey: %s     \n", text);
+      fflush(stdout);
+    } else if (!opt.quiet) {
+      printf("\r[+] Base minikey: %s     \r", text);
+      fflush(stdout);
+    }
+    // the carried group's minikeys are the first this chunk processes
+    for (const auto &h : carried) write_minikey(ctx, h);
+    carried.clear();
+    const uint64_t need = j->nseq - carry;
+    uint32_t nh = 0;
+    uint64_t ncand = 0, nvalid = 0;
+    r = kh_minikeys_scan(ctx, base, need, hits.data(), (uint32_t)hits.size(), &nh, &ncand, &nvalid);
+    if (r == KH_E_OVERFLOW && nh > hits.size()) {
+      hits.resize(nh);
+      r = kh_minikeys_scan(ctx, base, need, hits.data(), (uint32_t)hits.size(), &nh, &ncand, &nvalid);
+    }
+    if (r) {
+      fprintf(stderr, "[E] kh_minikeys_scan: %s (%s)\n", kh_strerror(r), kh_last_error(ctx));
+      break;
+    }
+    for (uint32_t i = 0; i < nh; i++) {
+      if (hits[i].ordinal < need)
+        write_minikey(ctx, hits[i]);
+      else
+        carried.push_back(hits[i]);
+    }
+    carry = nvalid - need;
+    g_groups_done += j->nseq / 1024;  // steps[thread]++ per 1024 valid minikeys (3253-3254)
+  }
+  j->rc = r;
+  kh_close(ctx);
+  g_running--;
+}
+
+void addr_worker(addr_job *j) {
+  kh_ctx *ctx = nullptr;
+  int r = open_with_targets(j, &ctx);
+  if (!ctx) {
+    j->rc = r;
+    g_running--;
+    return;
   }
   // --rmd-batch-size below 1024: the reference's groups of that size (thread_process,
   // keyhunt.cpp:3301-3307 -- FLAGMODE == MODE_RMD160 only), each counted as 1024 keys in the stats
@@ -1315,14 +1458,18 @@ void usage(const char *p) {
   printf("Usage: %s -m address|rmd160|xpoint|bsgs -f FILE [-b BITS | -r START:END] [-l compress|uncompress|both]\n"
          "       [-n N] [-k K] [-I STRIDE] [-g GPUS] [-q] [-s SECONDS] [-M] [-L blocked|reference]\n"
          "       [-e] [-c btc|eth] [-R] [-B sequential|backward|both|random|dance|angrygiant] [-S] [-6]\n"
-         "       [-z MULT] [-m vanity -v PREFIX ...] [--rmd-batch-size N] [-d] [-h]\n", p);
+         "       [-z MULT] [-m vanity -v PREFIX ...] [--rmd-batch-size N] [-d] [-h]\n"
+#ifdef KH_WITH_MINIKEYS
+         "       -m minikeys -f FILE [-C MINIKEY] [-8 ALPHABET] [-n N] [-R]\n"
+#endif
+         , p);
 }
 
 }  // namespace
 
 int main(int argc, char **argv) {
   printf("[+] Version %s\n", VERSION);
-  const char *mode_names[] = {"address", "rmd160", "xpoint", "bsgs", "vanity"};
+  const char *mode_names[] = {"address", "rmd160", "xpoint", "bsgs", "vanity", "minikeys"};
   int c;
   U order;
   u_from_hex(ORDER_HEX, order);
@@ -1351,8 +1498,44 @@ int main(int argc, char **argv) {
     opt.mapped_entries = n;
     opt.mapped_error = powl(0.5L, (long double)k);
   };
-  while ((c = getopt_long(argc, argv, "m:f:l:r:b:k:n:t:g:qs:I:L:MRec:B:S6v:z:dh", long_opts, nullptr)) != -1) {
+#ifdef KH_WITH_MINIKEYS
+  const char *short_opts = "m:f:l:r:b:k:n:t:g:qs:I:L:MRec:B:S6v:z:dhC:8:";
+  const int n_modes = 6;
+#else
+  const char *short_opts = "m:f:l:r:b:k:n:t:g:qs:I:L:MRec:B:S6v:z:dh";
+  const int n_modes = 5;
+#endif
+  while ((c = getopt_long(argc, argv, short_opts, long_opts, nullptr)) != -1) {
     switch (c) {
+#ifdef KH_WITH_MINIKEYS
+      case 'C':  // keyhunt.cpp:896-919: the raw digits through the alphabet as it stands (a -8 before it counts)
+        if (strlen(optarg) == 22) {
+          const char *alpha = opt.alphabet ? opt.alphabet : B58;
+          opt.have_minikey = true;
+          opt.minikey_str = optarg;
+          for (int i = 0; i < 21; i++) {
+            const char *p = strchr(alpha, optarg[i + 1]);
+            if (!p) {
+              fprintf(stderr, "[E] invalid character in minikey\n");
+              return EXIT_FAILURE;
+            }
+            g_mk_raw[i] = (uint8_t)((p - alpha) % 58);
+          }
+        } else {
+          fprintf(stderr, "[E] Invalid Minikey length %li : %s\n", (long)strlen(optarg), optarg);
+          return EXIT_FAILURE;
+        }
+        break;
+      case '8':  // keyhunt.cpp:1102-1110
+        if (strlen(optarg) == 58) {
+          opt.alphabet = optarg;
+          printf("[+] Base58 for Minikeys %s\n", opt.alphabet);
+        } else {
+          fprintf(stderr, "[E] The base58 alphabet must be 58 characters long.\n");
+          return EXIT_FAILURE;
+        }
+        break;
+#endif
       case 1:  // keyhunt.cpp:809-811: implies GGSB
         opt.ggsb_count = strtoull(optarg, NULL, 10);
         opt.ggsb = opt.ggsb_count > 0;
@@ -1426,7 +1609,7 @@ int main(int argc, char **argv) {
       }
       case 'm': {
         int m = -1;
-        for (int i = 0; i < 5; i++)
+        for (int i = 0; i < n_modes; i++)
           if (!strcmp(optarg, mode_names[i])) m = i;
         if (m < 0) {
           fprintf(stderr, "[E] Unsupported mode %s (engine covers address, rmd160, xpoint, bsgs, vanity)\n", optarg);
@@ -1668,7 +1851,17 @@ int main(int argc, char **argv) {
       if (nseq < 1024 || nseq % 1024) nseq = 0x100000000ULL;
     }
     printf("[+] N = %p\n", (void *)nseq);
-    print_range();
+    if (opt.mode == MODE_MINIKEYS) {  // keyhunt.cpp:1293-1323: the base if given, no range lines
+      if (opt.have_minikey) {
+        printf("[+] Base Minikey : %s\n", opt.minikey_str.c_str());
+      } else {  // a random base (3148-3157), drawn here instead of by the first worker
+        std::random_device rd;
+        for (int k = 0; k < 21; k++) g_mk_raw[k] = (uint8_t)((rd() & 0xFF) % 58);
+      }
+      minikey_n_init(nseq);
+    } else {
+      print_range();
+    }
     uint64_t items = 0;
     // -S: read the target cache if it exists (FLAGREADEDFILE1), else read the file and write it
     bool have_data = false;
@@ -1758,7 +1951,9 @@ int main(int argc, char **argv) {
                              : (opt.eth && (opt.mode == MODE_ADDRESS || opt.mode == MODE_RMD160)) ? KH_MODE_ETH
                                                                                                    : KH_MODE_ADDRESS;
       uint64_t need = 0;
-      if (kh_scan_memory(nseq, smode | (opt.endo ? KH_MODE_ENDO : 0), (uint32_t)opt.search, &need) == KH_OK) {
+      // (-m minikeys has no walk and no pad: a queue of a few MB per context)
+      if (opt.mode != MODE_MINIKEYS &&
+          kh_scan_memory(nseq, smode | (opt.endo ? KH_MODE_ENDO : 0), (uint32_t)opt.search, &need) == KH_OK) {
         for (int dev = 0; dev < ndev && dev < gpus; dev++) {
           const uint64_t per = (uint64_t)(gpus / ndev + (dev < gpus % ndev ? 1 : 0));
           uint64_t fr = 0, tot = 0;
@@ -1784,7 +1979,7 @@ int main(int argc, char **argv) {
         aj[d].data_file = data_file.c_str();
         aj[d].save_data = !have_data && d == 0;  // one GPU writes the cache
       }
-      th.emplace_back(addr_worker, &aj[d]);
+      th.emplace_back(opt.mode == MODE_MINIKEYS ? mini_worker : addr_worker, &aj[d]);
     }
   } else {
     FILE *f = fopen(opt.file, "r");
