@@ -13,11 +13,13 @@ for v in "${VARS[@]}"; do
   mkdir -p $d
   F="-O3 -std=c++17 -fPIC -I../include -Icsrc -DKH_WALK_LB=$lb -DKH_WALK_LB_HASH=$lbh -DKH_WALK_H=$h $rest"
   /opt/rocm/bin/hipcc --offload-arch=gfx950 $F -c csrc/kh_kernels.hip -o $d/k.o &
-  /opt/rocm/bin/hipcc --offload-host-only $F -c csrc/kh_capi.cpp -o $d/c.o &
+  for c in csrc/kh_capi*.cpp; do
+    /opt/rocm/bin/hipcc --offload-host-only $F -c $c -o $d/$(basename $c .cpp).o &
+  done
 done
 wait
 for v in "${VARS[@]}"; do
   d=../variants/$(name_of "$v")
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $d/libkh_gpu.so $d/k.o $d/c.o -Wl,-rpath,/opt/rocm/lib
-  rm -f $d/k.o $d/c.o
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $d/libkh_gpu.so $d/k.o $d/kh_capi*.o -Wl,-rpath,/opt/rocm/lib
+  rm -f $d/k.o $d/kh_capi*.o
 done
