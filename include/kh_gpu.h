@@ -302,6 +302,15 @@ int kh_tblk_check(kh_ctx *ctx, const uint8_t *items, uint32_t n, uint8_t *out);
 int kh_scan_device_hits(kh_ctx *ctx, uint32_t *device_hits, uint32_t *redos);
 /* copy a bloom back: layer 0 = target bloom, 1..3 = BSGS layers (256 shards concatenated, unpadded) */
 int kh_get_bloom(kh_ctx *ctx, uint32_t layer, uint8_t *buf, uint64_t cap, uint64_t *bytes);
+/* kh_get_bloom's counterpart for BSGS layer 1 (layer must be 1): after kh_bsgs_build / _load, replace the
+ * device's layer 1 by buf -- 256 shards concatenated, unpadded, exactly kh_get_bloom's byte count, in the
+ * layout kh_bsgs_setup chose.  A test puts a denser layer there (the built bits OR'ed with random ones),
+ * so that the first-level candidate list pins the giant walk at every offset.  Layers 2/3, the bP rows
+ * and lanes kept for a following call are untouched.  The host holds no copy of layer 1, so nothing is
+ * refreshed; kh_bsgs_save, which would write or rebuild the layer, returns KH_E_STATE afterwards until
+ * the next kh_bsgs_build / _load.  KH_E_STATE before the tables exist, KH_E_ARG for another layer or
+ * byte count. */
+int kh_bsgs_set_bloom(kh_ctx *ctx, uint32_t layer, const uint8_t *buf, uint64_t bytes);
 /* The context's own sorted bP rows (16 B each, the reference's bsgs_xvalue layout), valid until the
  * next kh_bsgs_build / _load / _set_table / kh_close: --ptable writes them to its file without a copy. */
 int kh_bsgs_table_rows(kh_ctx *ctx, const uint8_t **rows, uint64_t *n_rows);

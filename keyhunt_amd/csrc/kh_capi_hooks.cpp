@@ -360,6 +360,26 @@ int kh_get_bloom(kh_ctx *ctx, uint32_t layer, uint8_t *buf, uint64_t cap, uint64
   return KH_OK;
 }
 
+// kh_get_bloom's counterpart for BSGS layer 1: the caller's 256 unpadded shards onto the device layer at
+// its stride, in the layout kh_bsgs_setup chose.  Only the device bits change: the lanes a scan kept
+// stay valid (they do not depend on the layer), and the host holds no copy of layer 1 to refresh.
+// kh_bsgs_save would write these bits (reference layout) or rebuild the layer (blocked), so it refuses
+// until the next kh_bsgs_build / _load.
+int kh_bsgs_set_bloom(kh_ctx *ctx, uint32_t layer, const uint8_t *buf, uint64_t bytes) {
+  if (!ctx || !buf) return KH_E_ARG;
+  if (!ctx->bsgs_built) return KH_E_STATE;
+  const bloom_desc &d = ctx->bd[0];
+  if (layer != 1 || bytes != 256 * d.bytes) {
+    ctx->err = "kh_bsgs_set_bloom takes layer 1 and kh_get_bloom's byte count (" + std::to_string(256 * d.bytes) + ")";
+    return KH_E_ARG;
+  }
+  (void)hipSetDevice(ctx->device);
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpy2D(ctx->d_bl[0].get(), d.stride, buf, d.bytes, d.bytes, 256, hipMemcpyHostToDevice));
+  ctx->l1_replaced = true;
+  return KH_OK;
+}
+
 int kh_get_bsgs_table(kh_ctx *ctx, uint8_t *buf, uint64_t cap_rows, uint64_t *rows) {
   if (!ctx || !rows) return KH_E_ARG;
   if (!ctx->bsgs_built) return KH_E_STATE;

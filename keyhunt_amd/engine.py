@@ -128,6 +128,7 @@ def lib() -> ctypes.CDLL:
     L.kh_tblk_check.argtypes = [P, u8p, ctypes.c_uint32, u8p]
     L.kh_scan_device_hits.argtypes = [P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
     L.kh_get_bloom.argtypes = [P, ctypes.c_uint32, u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    L.kh_bsgs_set_bloom.argtypes = [P, ctypes.c_uint32, u8p, ctypes.c_uint64]
     L.kh_get_bsgs_table.argtypes = [P, u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
     L.kh_bsgs_set_table.argtypes = [P, u8p, ctypes.c_uint64]
     u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -495,6 +496,10 @@ class Engine:
         buf = ctypes.create_string_buffer(nb.value)
         self._chk(lib().kh_get_bloom(self._ctx, layer, buf, nb.value, ctypes.byref(nb)), "kh_get_bloom")
         return buf.raw
+
+    def set_bloom(self, layer: int, data: bytes) -> None:
+        """Parity hook: replace BSGS layer 1 on the device by `data` (get_bloom(1)'s size and layout)."""
+        self._chk(lib().kh_bsgs_set_bloom(self._ctx, layer, data, len(data)), "kh_bsgs_set_bloom")
 
     def get_bsgs_table(self) -> bytes:
         n = ctypes.c_uint64()

@@ -1166,11 +1166,14 @@ int or_bsgs_scan(const or_bsgs_params *p, const uint8_t *bf1, const uint8_t *bf2
                  uint64_t *cand_out, uint64_t cand_cap, uint64_t *n_cand) {
   return or_bsgs_scan_l1(p, bf1, 0, bf2, bf3, table, start_be, n_bases, qx, qy, key_out, cand_out, cand_cap, n_cand);
 }
-int or_bsgs_scan_l1(const or_bsgs_params *p, const uint8_t *bf1, uint64_t l1_blocks, const uint8_t *bf2,
-                    const uint8_t *bf3, const or_bxrow *table, const uint8_t start_be[32], uint64_t n_bases,
-                    const uint8_t qx[32], const uint8_t qy[32], uint8_t key_out[32],
-                    uint64_t *cand_out, uint64_t cand_cap, uint64_t *n_cand) {
-  bsgs_ctx c; bsgs_ctx_init(&c, p, bf1, bf2, bf3, table);
+/* the walk and the layer-1 probe of or_bsgs_scan_l1; refine = 0 lists the candidates only: no second
+ * check, so no key and no early stop (or_bsgs_l1_candidates) */
+static int bsgs_scan_walk(const or_bsgs_params *p, const uint8_t *bf1, uint64_t l1_blocks, const uint8_t *bf2,
+                          const uint8_t *bf3, const or_bxrow *table, const uint8_t start_be[32], uint64_t n_bases,
+                          const uint8_t qx[32], const uint8_t qy[32], uint8_t key_out[32],
+                          uint64_t *cand_out, uint64_t cand_cap, uint64_t *n_cand, int refine) {
+  bsgs_ctx c;
+  if (refine) bsgs_ctx_init(&c, p, bf1, bf2, bf3, table);
   ge Q; fe_from_be(&Q.x, qx); fe_from_be(&Q.y, qy); Q.inf = 0;
   /* GSn[i] = -(i+1)*2M*G, _2GSn = 2*GSn[511] (keyhunt.cpp:1797-1816) */
   walk_tab *t = (walk_tab *)malloc(sizeof(walk_tab));
@@ -1205,7 +1208,7 @@ int or_bsgs_scan_l1(const or_bsgs_params *p, const uint8_t *bf1, uint64_t l1_blo
           if (cand_out && nc < cand_cap) { cand_out[2 * nc] = b; cand_out[2 * nc + 1] = a; }
           nc++;
           fe key;
-          if (bsgs_second(&c, &base, a, &Q, &key)) { fe_to_be(key_out, &key); found = 1; }
+          if (refine && bsgs_second(&c, &base, a, &Q, &key)) { fe_to_be(key_out, &key); found = 1; }
         }
       }
       sp = nxt;
@@ -1215,6 +1218,25 @@ int or_bsgs_scan_l1(const or_bsgs_params *p, const uint8_t *bf1, uint64_t l1_blo
   if (n_cand) *n_cand = nc;
   free(pts); free(t);
   return found;
+}
+int or_bsgs_scan_l1(const or_bsgs_params *p, const uint8_t *bf1, uint64_t l1_blocks, const uint8_t *bf2,
+                    const uint8_t *bf3, const or_bxrow *table, const uint8_t start_be[32], uint64_t n_bases,
+                    const uint8_t qx[32], const uint8_t qy[32], uint8_t key_out[32],
+                    uint64_t *cand_out, uint64_t cand_cap, uint64_t *n_cand) {
+  return bsgs_scan_walk(p, bf1, l1_blocks, bf2, bf3, table, start_be, n_bases, qx, qy, key_out, cand_out, cand_cap,
+                        n_cand, 1);
+}
+/* or_bsgs_scan_l1 without bsgs_second: the same walk and layer-1 probe (both layouts) over all n_bases
+ * bases, every first-level candidate (base index, a) listed in order.  For layers dense enough that a
+ * second check per candidate (two scalar multiplications and 32 additions) would dominate.  Returns the
+ * candidate count (also in *n_cand); cand_out holds the first cand_cap of them. */
+uint64_t or_bsgs_l1_candidates(const or_bsgs_params *p, const uint8_t *bf1, uint64_t l1_blocks,
+                               const uint8_t start_be[32], uint64_t n_bases, const uint8_t qx[32],
+                               const uint8_t qy[32], uint64_t *cand_out, uint64_t cand_cap, uint64_t *n_cand) {
+  uint64_t nc = 0;
+  bsgs_scan_walk(p, bf1, l1_blocks, 0, 0, 0, start_be, n_bases, qx, qy, 0, cand_out, cand_cap, &nc, 0);
+  if (n_cand) *n_cand = nc;
+  return nc;
 }
 
 /* ------------------------------------------------------------------------------------------ */

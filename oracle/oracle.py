@@ -35,6 +35,7 @@ def lib():
         L.or_bloom_entries.restype = ctypes.c_uint64
         L.or_bloom_entries.argtypes = [ctypes.c_uint64]
         L.or_bsgs_giant_probe.restype = ctypes.c_uint64
+        L.or_bsgs_l1_candidates.restype = ctypes.c_uint64
         _lib = L
     return _lib
 
@@ -282,6 +283,20 @@ class BsgsTables:
         nc = min(ncand.value, cand_cap)
         cl = [(cands[2 * i], cands[2 * i + 1]) for i in range(nc)]
         return (int.from_bytes(key.raw, "big") if found else None), cl
+
+    def candidates(self, start: int, n_bases: int, q: tuple[int, int], cap: int = 1 << 17):
+        """scan() without the second checks (or_bsgs_l1_candidates): every first-level candidate
+        (base index, a) of all n_bases bases, in walk order -- no key, no early stop.  For a layer 1
+        dense enough that scan()'s second check per candidate would dominate."""
+        cands = (ctypes.c_uint64 * (2 * cap))()
+        ncand = ctypes.c_uint64()
+        lib().or_bsgs_l1_candidates(ctypes.byref(self.p), self.bf1, ctypes.c_uint64(self.l1_blocks), be32(start),
+                                    ctypes.c_uint64(n_bases), be32(q[0]), be32(q[1]), cands,
+                                    ctypes.c_uint64(cap), ctypes.byref(ncand))
+        if ncand.value > cap:
+            raise OverflowError(f"{ncand.value} candidates, cap {cap}")
+        flat = cands[: 2 * ncand.value]
+        return list(zip(flat[0::2], flat[1::2]))
 
     def refine(self, base: int, a: int, q: tuple[int, int]):
         key = ctypes.create_string_buffer(32)

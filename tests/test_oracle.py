@@ -242,3 +242,28 @@ def test_oracle_blocked_layer1_check_vs_spec_model(oracle):
     # a random X passes iff all 16 of its bits are set: the model says so too
     exp = sum(all(model[o] & b for o, b in words(xb)) for xb in rnd)
     assert hits == exp and hits < 200
+
+
+@pytest.mark.parametrize("blocked", [False, True], ids=["reference", "blocked"])
+def test_oracle_candidates_equal_scan_candidates(oracle, blocked):
+    """BsgsTables.candidates (or_bsgs_l1_candidates: the walk and the layer-1 probe alone) lists what
+    scan() lists, in both layer-1 layouts: n = 2^24, k = 3 (overlapping bases) over 8 bases = 16384
+    giant points, a far target, and a layer 1 made dense enough (built bits OR random ones, ~2 % of
+    points pass) for a few hundred candidates."""
+    from _dense_layer import dense_layer
+    p = oracle.bsgs_params(1 << 24, 3)
+    t = oracle.BsgsTables(p)
+    blocks = (p.bits[0] * 3 + 127) // 128 if blocked else 0
+    built = bytes(256 * 16 * blocks) if blocked else t.bf1.raw
+    l1 = dense_layer(built, 0.02, blocked, p.hashes[0], seed=24 + blocked)
+    tabs = oracle.BsgsTables.from_raw(p, l1, t.bf2.raw, t.bf3.raw, t.table_bytes(), l1_blocks=blocks)
+    start = 0x6B6B6B6B0000000
+    q = oracle.pubkey(start - 99991 * 2 * p.n)          # far: no base holds it
+    key, via_scan = tabs.scan(start, 8, q)
+    assert key is None
+    cands = tabs.candidates(start, 8, q)
+    assert cands == via_scan
+    assert 200 <= len(cands) <= 500                     # 16384 x 2 % = 328
+    assert {b for b, _ in cands} == set(range(8)) and max(a for _, a in cands) < p.cycles * 1024
+    with pytest.raises(OverflowError):
+        tabs.candidates(start, 8, q, cap=len(cands) - 1)
