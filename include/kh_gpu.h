@@ -177,7 +177,7 @@ int kh_set_rmd_batch(kh_ctx *ctx, uint32_t group);
 typedef struct {
   uint8_t key[32];      /* SHA-256(minikey) as the reference prints it: not reduced mod n */
   uint64_t offset;      /* candidate number, 1-based from the base */
-  uint32_t ordinal;     /* 0-based index among the call's valid candidates */
+  uint64_t ordinal;     /* 0-based index among the call's valid candidates (need_valid can be 2^32) */
   char minikey[24];     /* the 22 characters, NUL-terminated */
 } kh_minikey_hit;
 /* -8: the 58 characters (NULL = KH_MINIKEY_ALPHABET) */

@@ -190,7 +190,7 @@ int kh_minikeys_scan(kh_ctx *ctx, const uint8_t base[21], uint64_t need_valid, k
       o.offset = h.idx;
       uint64_t before = 0;
       for (uint64_t v : q) before += v < h.idx;
-      o.ordinal = (uint32_t)(seen + before);
+      o.ordinal = seen + before;
       out.push_back(o);
     }
     if (end) {

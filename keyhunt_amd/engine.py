@@ -49,7 +49,7 @@ class KhBsgsFound(ctypes.Structure):
 
 
 class KhMinikeyHit(ctypes.Structure):
-    _fields_ = [("key", ctypes.c_uint8 * 32), ("offset", ctypes.c_uint64), ("ordinal", ctypes.c_uint32),
+    _fields_ = [("key", ctypes.c_uint8 * 32), ("offset", ctypes.c_uint64), ("ordinal", ctypes.c_uint64),
                 ("minikey", ctypes.c_char * 24)]
 
 
@@ -301,10 +301,11 @@ class Engine:
         self._chk(r, "kh_minikeys_scan")
         return out, nc, nv
 
-    def minikeys_valid(self, base: list[int], n_candidates: int) -> list[int]:
-        """The valid candidates among base+1 .. base+n_candidates, ascending (the filter kernel)."""
+    def minikeys_valid(self, base: list[int], n_candidates: int, cap: int = 0) -> list[int]:
+        """The valid candidates among base+1 .. base+n_candidates, ascending (the filter kernel).  With
+        more than `cap` of them (0 = n_candidates / 128 + 64) the call is made a second time."""
         n = ctypes.c_uint64(0)
-        cap = n_candidates // 128 + 64
+        cap = cap or n_candidates // 128 + 64
         buf = (ctypes.c_uint64 * cap)()
         r = lib().kh_minikeys_valid(self._ctx, bytes(base), n_candidates, buf, cap, ctypes.byref(n))
         if r == KH_E_OVERFLOW:

@@ -9,6 +9,7 @@ at least N valid candidates; the next chunk's base is base + 253*N (increment_mi
 """
 from __future__ import annotations
 
+import functools
 import hashlib
 import os
 import sys
@@ -79,6 +80,7 @@ def valid_offsets(base: list[int], n_candidates: int, alphabet: str = ALPHABET) 
     return [off for off, mk in walk(base, n_candidates, alphabet) if is_valid(mk)]
 
 
+@functools.lru_cache(maxsize=None)
 def h160_of_key(key: int) -> bytes:
     import oracle
     x, y = oracle.pubkey(key % oracle.SECP_N)

@@ -35,6 +35,12 @@ def test_abi_version_and_errors():
     assert L.kh_strerror(-6).startswith(b"BSGS n")
 
 
+def test_minikey_hit_ordinal_is_64_bit_in_the_header():
+    """need_valid can be 2^32 (the CLI's default -n): the carried group's ordinals do not fit 32 bits."""
+    struct = re.search(r"typedef struct \{([^}]*)\} kh_minikey_hit;", open(E.HEADER).read()).group(1)
+    assert re.search(r"^\s*uint64_t ordinal;", struct, re.M) and "uint32_t" not in struct
+
+
 def test_null_context_is_rejected():
     L = keyhunt_amd.lib()
     n = ctypes.c_uint32()

@@ -114,3 +114,70 @@ def test_null_context_is_rejected():
     assert L.kh_minikeys_scan(None, bytes(21), 1, None, 0, ctypes.byref(n), ctypes.byref(nc), ctypes.byref(nv)) == -1
     assert L.kh_minikeys_valid(None, bytes(21), 4, None, 0, ctypes.byref(nc)) == -1
     assert L.kh_minikeys_set_alphabet(None, None) == -1 and L.kh_minikeys_set_window(None, 0, 0) == -1
+
+
+# -- the dense construction and the 2^32 crossing (tests/test_gpu_minikeys_dense.py) -----------------------
+# A many-to-one alphabet: digits 8..57 all spell 'A', so every candidate whose changed digits are >= 8
+# spells the same string, and one valid string makes a whole run of candidates valid.
+DENSE_ALPHA = M.ALPHABET[:8] + "A" * 50
+DENSE_BASE = [16, 0, 3, 41, 52, 35, 57, 22, 38, 41, 37, 28, 38, 33, 46, 31, 15, 10, 0, 0, 0]  # raw digits
+DENSE_KEY = "SA14AAAAAAAAAAAAAAAAAA"
+FILTER_BLOCK = 58 * 256  # candidates of one k_mini_filter block: 256 rows of 58
+EXAMPLE = "SG64GZqySYwBm9KxE3wH8R"
+X32 = 1 << 32
+_cache = {}
+
+
+def dense_valid() -> list[int]:
+    """The model's valid candidates of the first 2^18 from DENSE_BASE: computed once, never changed."""
+    if "dense" not in _cache:
+        _cache["dense"] = tuple(M.valid_offsets(DENSE_BASE, 1 << 18, DENSE_ALPHA))
+    return list(_cache["dense"])
+
+
+def around_x32() -> list[tuple[int, str]]:
+    """(offset, minikey) of the example base's valid candidates in (2^32 - 2^15, 2^32 + 2^15], from the
+    base shifted by 2^32 - 2^15."""
+    if "x32" not in _cache:
+        lo = X32 - (1 << 15)
+        shifted = M.digits_from_value(M.value_of(M.digits_of(EXAMPLE)) + lo)
+        _cache["x32"] = tuple((lo + o, mk) for o, mk in M.walk(shifted, 1 << 16) if M.is_valid(mk))
+    return list(_cache["x32"])
+
+
+def test_dense_construction_counts():
+    """What the dense GPU tests rest on: blocks of the first launch that overflow the filter's 256-entry
+    stage beside blocks that do not."""
+    assert M.text_of(DENSE_BASE, DENSE_ALPHA) == "SA14AAAAAAAAAAAAAAA111" and M.is_valid(DENSE_KEY)
+    v = dense_valid()
+    assert len(v) == 157987 and sum(o <= 1 << 16 for o in v) == 29148
+    # DENSE_BASE[20] == 0: block k of the window (0, 2^18] holds candidates [k * 14848, (k + 1) * 14848)
+    per_block = [0] * 18
+    for o in v:
+        per_block[o // FILTER_BLOCK] += 1
+    assert ((1 << 18) + FILTER_BLOCK) // FILTER_BLOCK == 18
+    assert (min(per_block), max(per_block)) == (51, 11400) and sum(n > 256 for n in per_block) == 16
+    assert (per_block[0], per_block[2]) == (51, 11050)  # one-block windows: from the base, and from base + 2 blocks
+    # every candidate whose last three digits are all >= 8 spells the dense key
+    assert all(M.candidate(DENSE_BASE, o, DENSE_ALPHA) == DENSE_KEY
+               for o in (8 * 58 * 58 + 8 * 58 + 8, 57 * 58 * 58 + 57 * 58 + 57))
+    strings = {M.candidate(DENSE_BASE, o, DENSE_ALPHA) for o in v if o <= 1 << 16}
+    assert len(strings) == 4 and DENSE_KEY in strings
+    # the dense scan: the 4096-th valid candidate, inside the first 2^16
+    assert v[4095] == 32416 and M.scan(DENSE_BASE, 4096, set(), DENSE_ALPHA)[:2] == (32416, 4096)
+
+
+def test_valid_candidates_around_2_to_32():
+    got = around_x32()
+    assert len(got) == 275 and [o for o, _ in got] == sorted(o for o, _ in got)
+    below = [(o, mk) for o, mk in got if o <= X32]
+    assert below[-1] == (4294966823, "SG64GZqySYwBm9KxLbU78Y") and got[len(below)] == (4294967552, "SG64GZqySYwBm9KxLbU7M7")
+    assert all(M.candidate(M.digits_of(EXAMPLE), o) == mk for o, mk in (got[0], below[-1], got[len(below)], got[-1]))
+
+
+def test_minikey_hit_layout():
+    """kh_minikey_hit: ordinal is 64 bits (need_valid can be 2^32); the struct keeps its 72 bytes."""
+    H = keyhunt_amd.KhMinikeyHit
+    assert ctypes.sizeof(H) == 72
+    assert (H.key.offset, H.offset.offset, H.ordinal.offset, H.ordinal.size) == (0, 32, 40, 8)
+    assert (H.minikey.offset, H.minikey.size) == (48, 24)
