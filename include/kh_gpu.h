@@ -271,6 +271,28 @@ int kh_kernel_time_reset(kh_ctx *ctx);
 /* ---- parity hooks (used by tests/) -------------------------------------------------------- */
 /* k*G for n scalars (big-endian 32 B each) -> n x {x,y} (big-endian), through the lane-setup kernel */
 int kh_pubkeys(kh_ctx *ctx, const uint8_t *scalars, uint32_t n, uint8_t *xy);
+/* The lane-setup kernel (k_setup) in each of its forms, on buffers of the hook's own: the centres
+ * C_g = [Q +] s_g*G of L lanes (at most 2^22) -> L x {x,y} (big-endian).  q: the point Q as {x[32], y[32]}
+ * or null.  The context's lanes and whatever a scan kept are untouched, and no BSGS tables are needed.
+ *   prog 0: s_g = scalars[g] (L x 32 B big-endian, none 0 mod n);
+ *   prog 1: s_g = s0 + g*step (mod n), derived on the device; KH_E_ARG when a lane's scalar is 0 mod n;
+ *   prog 2: the BSGS centres.  Lane g starts at giant index t0 = t_round + g*lane_pts, base b = t0 / a_pts,
+ *           a0 = t0 % a_pts, and s_g = -(base(b) + m*(2*(a0 + h) + 1)) mod n with base(b) = list[b]
+ *           (n_bases x 32 B big-endian) or, with list null, start + b*two_n.  All values are taken raw (a
+ *           base in [n, 2^256) is summed right mod n, though the engine never sends one).
+ * Every index the kernel will form is checked first: KH_E_ARG when the last lane's base is not below
+ * n_bases (list form), when a sum leaves 64 bits, or when a lane's centre key is 0 mod n. */
+typedef struct kh_setup_form {
+  uint32_t prog, L;
+  const uint8_t *scalars;          /* prog 0 */
+  uint8_t s0[32], step[32];        /* prog 1 */
+  const uint8_t *list;             /* prog 2: list form, or null */
+  uint64_t n_bases;
+  uint8_t start[32];               /* prog 2: continuous form */
+  uint64_t t_round, lane_pts, a_pts, two_n, m;
+  uint32_t h;
+} kh_setup_form;
+int kh_setup_centres(kh_ctx *ctx, const kh_setup_form *form, const uint8_t *q, uint8_t *xy);
 /* X (and Y if out_y) of points start + i*stride, i < n_points (multiple of 1024), via the walk */
 int kh_walk_points(kh_ctx *ctx, const uint8_t start[32], const uint8_t stride[32], uint64_t n_points,
                    uint8_t *out_x, uint8_t *out_y);
@@ -302,14 +324,15 @@ int kh_tblk_check(kh_ctx *ctx, const uint8_t *items, uint32_t n, uint8_t *out);
 int kh_scan_device_hits(kh_ctx *ctx, uint32_t *device_hits, uint32_t *redos);
 /* copy a bloom back: layer 0 = target bloom, 1..3 = BSGS layers (256 shards concatenated, unpadded) */
 int kh_get_bloom(kh_ctx *ctx, uint32_t layer, uint8_t *buf, uint64_t cap, uint64_t *bytes);
-/* kh_get_bloom's counterpart for BSGS layer 1 (layer must be 1): after kh_bsgs_build / _load, replace the
- * device's layer 1 by buf -- 256 shards concatenated, unpadded, exactly kh_get_bloom's byte count, in the
- * layout kh_bsgs_setup chose.  A test puts a denser layer there (the built bits OR'ed with random ones),
- * so that the first-level candidate list pins the giant walk at every offset.  Layers 2/3, the bP rows
- * and lanes kept for a following call are untouched.  The host holds no copy of layer 1, so nothing is
- * refreshed; kh_bsgs_save, which would write or rebuild the layer, returns KH_E_STATE afterwards until
- * the next kh_bsgs_build / _load.  KH_E_STATE before the tables exist, KH_E_ARG for another layer or
- * byte count. */
+/* kh_get_bloom's counterpart for BSGS layers 1 and 2: after kh_bsgs_build / _load, replace the layer by
+ * buf -- 256 shards concatenated, unpadded, exactly kh_get_bloom's byte count (layer 1: in the layout
+ * kh_bsgs_setup chose).  A test puts a denser layer there (the built bits OR'ed with random ones), so that
+ * the first-level candidate list pins the giant walk at every offset (layer 1) and the second check's
+ * masks pin all 32 of its points (layer 2).  The other layers, the bP rows and lanes kept for a following
+ * call are untouched.  The host holds no copy of layer 1; its copy of layer 2 (the host second check's)
+ * is replaced along with the device's.  kh_bsgs_save, which would write or rebuild the layer, returns
+ * KH_E_STATE afterwards until the next kh_bsgs_build / _load.  KH_E_STATE before the tables exist,
+ * KH_E_ARG for layer 3 (or any other) or another byte count. */
 int kh_bsgs_set_bloom(kh_ctx *ctx, uint32_t layer, const uint8_t *buf, uint64_t bytes);
 /* The context's own sorted bP rows (16 B each, the reference's bsgs_xvalue layout), valid until the
  * next kh_bsgs_build / _load / _set_table / kh_close: --ptable writes them to its file without a copy. */
@@ -343,6 +366,16 @@ int kh_bsgs_get_candidates(kh_ctx *ctx, uint64_t *base_index, uint32_t *a, uint3
  * Q - base_key*G + AMP2[i] passes bloom_bPx2nd (keyhunt.cpp:5151-5184) */
 int kh_bsgs_second_masks(kh_ctx *ctx, uint32_t target, const uint8_t *base_keys, uint32_t n, uint32_t *gpu_mask,
                          uint32_t *host_mask);
+/* The same through the kernel's own index arithmetic, in both of its forms.  Candidate j has giant index
+ * t = t_round + idx[j], base b = t / a_pts, a = t % a_pts and base key base(b) + a*2M (mod n), with base(b)
+ * = list[b] (n_bases x 32 B big-endian) or, with list null, start + b*two_n.  gpu_mask: k_refine's masks;
+ * host_mask: the host code's for the same base keys, computed with 256-bit host arithmetic.  A base key of
+ * 0 mod n has no point: both masks are 0.  two_m = 0 stands for the tables' 2M; start, the list and two_m
+ * are taken raw (a base in [n, 2^256) is summed right mod n, though the engine never sends one).  KH_E_ARG
+ * when a candidate's base is not below n_bases (list form) or t leaves 64 bits; nothing is launched then. */
+int kh_bsgs_refine_masks(kh_ctx *ctx, uint32_t target, const uint8_t start[32], const uint8_t *list, uint64_t n_bases,
+                         uint64_t t_round, uint64_t a_pts, uint64_t two_n, uint64_t two_m, const uint64_t *idx,
+                         uint32_t n, uint32_t *gpu_mask, uint32_t *host_mask);
 /* sorted bP table as the reference's 16-byte bsgs_xvalue rows {value[6], pad[2], index u64 LE} */
 int kh_get_bsgs_table(kh_ctx *ctx, uint8_t *buf, uint64_t cap_rows, uint64_t *rows);
 /* --ptable FILE --load-ptable (keyhunt.cpp:1847-1956): after kh_bsgs_build (or _load), replace the

@@ -94,7 +94,7 @@ extern "C" int kh_bsgs_setup(kh_ctx *ctx, uint64_t n, uint64_t k, kh_bsgs_info *
   ctx->second_hits = 0;
   ctx->bsgs_ready = true;
   ctx->bsgs_built = false;
-  ctx->l1_replaced = false;
+  ctx->layer_replaced = false;
   ctx->candidates = 0;
   ctx->second_hits = 0;
   if (info) *info = I;
@@ -202,7 +202,7 @@ extern "C" int kh_bsgs_build(kh_ctx *ctx) {
     KHTRY(download(ctx, ctx->h_bl[l].data(), ctx->d_bl[l], ctx->h_bl[l].size()));
   }
   ctx->bsgs_built = true;
-  ctx->l1_replaced = false;
+  ctx->layer_replaced = false;
   return KH_OK;
 }
 
@@ -310,8 +310,8 @@ int ref_layer1(kh_ctx *c, std::vector<uint8_t> &out) {
 extern "C" int kh_bsgs_save(kh_ctx *ctx, const char *dir) {
   if (!ctx) return KH_E_ARG;
   if (!ctx->bsgs_built) return KH_E_STATE;
-  if (ctx->l1_replaced) {
-    ctx->err = "layer 1 was replaced by kh_bsgs_set_bloom: build or load the tables again before saving them";
+  if (ctx->layer_replaced) {
+    ctx->err = "a layer was replaced by kh_bsgs_set_bloom: build or load the tables again before saving them";
     return KH_E_STATE;
   }
   (void)hipSetDevice(ctx->device);
@@ -400,7 +400,7 @@ extern "C" int kh_bsgs_load(kh_ctx *ctx, const char *dir, uint32_t flags) {
   }
   ctx->h_rows.swap(rows);
   ctx->bsgs_built = true;
-  ctx->l1_replaced = false;
+  ctx->layer_replaced = false;
   return KH_OK;
 }
 

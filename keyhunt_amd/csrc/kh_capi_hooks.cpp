@@ -161,6 +161,84 @@ int kh_bsgs_second_masks(kh_ctx *ctx, uint32_t target, const uint8_t *base_keys,
   return KH_OK;
 }
 
+// kh_bsgs_second_masks over k_refine's own index arithmetic: candidate j has giant index t = t_round +
+// idx[j], base b = t / a_pts and a = t % a_pts, and its base key is base(b) + a*2M with base(b) =
+// start + b*two_n (list == null) or list[b].  Every b is checked against n_bases before the launch.
+int kh_bsgs_refine_masks(kh_ctx *ctx, uint32_t target, const uint8_t start[32], const uint8_t *list, uint64_t n_bases,
+                         uint64_t t_round, uint64_t a_pts, uint64_t two_n, uint64_t two_m_raw, const uint64_t *idx,
+                         uint32_t n, uint32_t *gpu_mask, uint32_t *host_mask) {
+  if (!ctx || (!start && !list) || !idx || !gpu_mask || !host_mask || !a_pts || (list && !n_bases)) return KH_E_ARG;
+  if (!ctx->bsgs_built || target >= ctx->targets.size()) return KH_E_STATE;
+  if (n == 0) return KH_OK;
+  (void)hipSetDevice(ctx->device);
+  const ge &Q = ctx->targets[target];
+  const uint64_t two_m = two_m_raw ? two_m_raw : 2 * ctx->info.m;
+  // the bases go to the device as given; the kernel's sum is right mod n for any 256-bit base, since base
+  // + offset < 2^256 + 2^129 < 2n (the engine itself sends reduced ones)
+  const u256 st = start ? u256_from_be(start) : u256{};
+  std::vector<uint32_t> lw;
+  if (list) {
+    lw.resize((size_t)n_bases * 8);
+    for (uint64_t b = 0; b < n_bases; b++) u256_to_limbs(&lw[(size_t)b * 8], u256_from_be(list + b * 32));
+  }
+  std::vector<kh_dev_hit> c(n);
+  for (uint32_t j = 0; j < n; j++) {
+    const u128 t = (u128)t_round + idx[j];
+    if (t >> 64) return KH_E_ARG;  // the kernel's 64-bit sum would wrap
+    const uint64_t b = (uint64_t)t / a_pts, a = (uint64_t)t % a_pts;
+    if (list && b >= n_bases) {
+      ctx->err = "kh_bsgs_refine_masks: candidate " + std::to_string(j) + " lies in base " + std::to_string(b) +
+                 " of " + std::to_string(n_bases);
+      return KH_E_ARG;
+    }
+    u256 k;
+    if (list) {
+      memcpy(&k, &lw[(size_t)b * 8], 32);  // 8 LE u32 limbs = 4 LE u64 limbs
+      k = sc_reduce(k);
+    } else {
+      k = sc_add(sc_reduce(st), sc_reduce(u256_from_u128((u128)b * two_n)));
+    }
+    k = sc_add(k, sc_reduce(u256_from_u128((u128)a * two_m)));
+    c[j].idx = idx[j];
+    c[j].kind = 4;
+    c[j].aux = 0xFFFFFFFFu;
+    host_mask[j] = second_mask(ctx, k, Q);
+  }
+  uint32_t Qw[16], sw[8];
+  memcpy(Qw, Q.x.d, 32);
+  memcpy(Qw + 8, Q.y.d, 32);
+  u256_to_limbs(sw, st);
+  dev_buf<uint32_t> d_list, d_start, d_q, d_cnt;
+  dev_buf<kh_dev_hit> d_c;
+  if (list) KHTRY(upload(ctx, d_list, lw.data(), lw.size()));
+  KHTRY(upload(ctx, d_start, sw, 8));
+  KHTRY(upload(ctx, d_q, Qw, 16));
+  KHTRY(upload(ctx, d_cnt, &n, 1));
+  KHTRY(upload(ctx, d_c, c.data(), n));
+  refine_args Ra;
+  memset(&Ra, 0, sizeof Ra);
+  Ra.cands = d_c.get();
+  Ra.count = d_cnt.get();
+  Ra.cap = n;
+  Ra.list_mode = list ? 1 : 0;
+  Ra.t_round = t_round;
+  Ra.a_pts = a_pts;
+  Ra.two_n = two_n;
+  Ra.two_m = two_m;
+  Ra.start = d_start.get();
+  Ra.list = d_list.get();
+  Ra.comb = ctx->d_comb.get();
+  Ra.q = d_q.get();
+  Ra.amp2 = ctx->d_amp2.get();
+  Ra.bloom2 = ctx->d_bl[1].get();
+  Ra.bd2 = ctx->bd[1];
+  HIPCHK(ctx, launch_refine(Ra, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  KHTRY(download(ctx, c.data(), d_c, n));
+  for (uint32_t j = 0; j < n; j++) gpu_mask[j] = c[j].aux;
+  return KH_OK;
+}
+
 int kh_kernel_time(kh_ctx *ctx, uint32_t kind, uint64_t *launches, double *ms, uint64_t *points) {
   if (!ctx || kind > 6) return KH_E_ARG;
   if (launches) *launches = ctx->tm[kind].launches;
@@ -200,6 +278,126 @@ int kh_pubkeys(kh_ctx *ctx, const uint8_t *scalars, uint32_t n, uint8_t *xy) {
     }
     fe_to_be(xy + 64 * i, x);
     fe_to_be(xy + 64 * i + 32, y);
+  }
+  return KH_OK;
+}
+
+// k_setup on buffers of the hook's own: the context's lanes, pad and kept state are not touched.  Every
+// index the kernel forms is checked here first: scalars and centres hold L entries, and the list form
+// reads base (t_round + g*lane_pts) / a_pts for g < L, the largest at g = L - 1.
+int kh_setup_centres(kh_ctx *ctx, const kh_setup_form *f, const uint8_t *q, uint8_t *xy) {
+  if (!ctx || !f || !xy || !f->L || f->L > (1u << 22) || f->prog > 2) return KH_E_ARG;
+  const uint32_t L = f->L;
+  std::vector<uint32_t> up;  // prog 0: the scalars; prog 2: the list
+  setup_args A;
+  memset(&A, 0, sizeof A);
+  u256 st{};
+  if (f->prog == 0) {
+    if (!f->scalars) return KH_E_ARG;
+    up.resize((size_t)L * 8);
+    for (uint32_t g = 0; g < L; g++) {
+      const u256 k = sc_reduce(u256_from_be(f->scalars + (size_t)g * 32));
+      if (u256_is_zero(k)) return KH_E_ARG;
+      u256_to_limbs(&up[(size_t)g * 8], k);
+    }
+  } else if (f->prog == 1) {
+    u256_to_limbs(A.s0, sc_reduce(u256_from_be(f->s0)));
+    u256_to_limbs(A.step, sc_reduce(u256_from_be(f->step)));
+  } else {
+    // 2*(a0 + h) + 1 with a0 < a_pts must fit 64 bits, and so must the last lane's giant index
+    if (!f->lane_pts || !f->a_pts || !f->m || f->a_pts >> 61 || (f->list && !f->n_bases)) return KH_E_ARG;
+    const u128 t_last = (u128)f->t_round + (u128)(L - 1) * f->lane_pts;
+    if (t_last >> 64) return KH_E_ARG;
+    if (f->list && (uint64_t)t_last / f->a_pts >= f->n_bases) {
+      ctx->err = "kh_setup_centres: the last lane lies in base " + std::to_string((uint64_t)t_last / f->a_pts) +
+                 " of " + std::to_string(f->n_bases);
+      return KH_E_ARG;
+    }
+    // the bases go to the device as given: the kernel's sum is right mod n for any 256-bit base, since
+    // base + offset < 2^256 + 2^129 < 2n (the engine itself sends reduced ones)
+    st = u256_from_be(f->start);
+    if (f->list) {
+      up.resize((size_t)f->n_bases * 8);
+      for (uint64_t b = 0; b < f->n_bases; b++) u256_to_limbs(&up[(size_t)b * 8], u256_from_be(f->list + b * 32));
+    }
+    // a centre key of 0 mod n has no point (the engine keeps such rounds on the host)
+    for (uint32_t g = 0; g < L; g++) {
+      const uint64_t t0 = f->t_round + (uint64_t)g * f->lane_pts, b = t0 / f->a_pts, a0 = t0 % f->a_pts;
+      u256 k;
+      if (f->list) {
+        memcpy(&k, &up[(size_t)b * 8], 32);  // 8 LE u32 limbs = 4 LE u64 limbs
+        k = sc_reduce(k);
+      } else {
+        k = sc_add(sc_reduce(st), sc_reduce(u256_from_u128((u128)b * f->two_n)));
+      }
+      k = sc_add(k, sc_reduce(u256_from_u128((u128)f->m * (2 * (a0 + f->h) + 1))));
+      if (u256_is_zero(k)) {
+        ctx->err = "kh_setup_centres: lane " + std::to_string(g) + " has centre key 0 mod n";
+        return KH_E_ARG;
+      }
+    }
+  }
+  (void)hipSetDevice(ctx->device);
+  dev_buf<uint32_t> d_up, d_start, d_q, d_zero, d_cx, d_cy;
+  if (!up.empty()) KHTRY(upload(ctx, d_up, up.data(), up.size()));
+  KHTRY(d_cx.reserve(ctx, (size_t)L * 8));
+  KHTRY(d_cy.reserve(ctx, (size_t)L * 8));
+  A.comb = ctx->d_comb.get();
+  A.L = L;
+  A.cx = d_cx.get();
+  A.cy = d_cy.get();
+  A.prog = f->prog;
+  if (f->prog == 0) A.scalars = d_up.get();
+  if (f->prog == 1) {
+    const uint32_t zero = 0;
+    KHTRY(upload(ctx, d_zero, &zero, 1));
+    A.zero_flag = d_zero.get();
+  }
+  if (f->prog == 2) {
+    uint32_t sw[8];
+    u256_to_limbs(sw, st);
+    KHTRY(upload(ctx, d_start, sw, 8));
+    A.start = d_start.get();
+    A.list = f->list ? d_up.get() : nullptr;
+    A.t_round = f->t_round;
+    A.lane_pts = f->lane_pts;
+    A.a_pts = f->a_pts;
+    A.two_n = f->two_n;
+    A.m = f->m;
+    A.h = f->h;
+  }
+  if (q) {
+    uint32_t Qw[16];
+    fe x, y;
+    fe_from_be(x, q);
+    fe_from_be(y, q + 32);
+    memcpy(Qw, x.d, 32);
+    memcpy(Qw + 8, y.d, 32);
+    KHTRY(upload(ctx, d_q, Qw, 16));
+    A.q = d_q.get();
+    A.has_q = 1;
+  }
+  HIPCHK(ctx, launch_setup(A, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (f->prog == 1) {
+    uint32_t zero = 0;
+    KHTRY(download(ctx, &zero, d_zero, 1));
+    if (zero) {
+      ctx->err = "lane centre scalar is 0 mod n";
+      return KH_E_ARG;
+    }
+  }
+  std::vector<uint32_t> cx((size_t)L * 8), cy((size_t)L * 8);
+  KHTRY(download(ctx, cx.data(), d_cx, cx.size()));
+  KHTRY(download(ctx, cy.data(), d_cy, cy.size()));
+  for (uint32_t i = 0; i < L; i++) {
+    fe x, y;
+    for (int w = 0; w < 8; w++) {
+      x.d[w] = cx[(size_t)w * L + i];
+      y.d[w] = cy[(size_t)w * L + i];
+    }
+    fe_to_be(xy + 64 * (size_t)i, x);
+    fe_to_be(xy + 64 * (size_t)i + 32, y);
   }
   return KH_OK;
 }
@@ -360,23 +558,33 @@ int kh_get_bloom(kh_ctx *ctx, uint32_t layer, uint8_t *buf, uint64_t cap, uint64
   return KH_OK;
 }
 
-// kh_get_bloom's counterpart for BSGS layer 1: the caller's 256 unpadded shards onto the device layer at
-// its stride, in the layout kh_bsgs_setup chose.  Only the device bits change: the lanes a scan kept
-// stay valid (they do not depend on the layer), and the host holds no copy of layer 1 to refresh.
-// kh_bsgs_save would write these bits (reference layout) or rebuild the layer (blocked), so it refuses
-// until the next kh_bsgs_build / _load.
+// kh_get_bloom's counterpart for BSGS layers 1 and 2: the caller's 256 unpadded shards onto the device
+// layer at its stride (layer 1: in the layout kh_bsgs_setup chose).  The lanes a scan kept stay valid
+// (they do not depend on the layers).  The host holds no copy of layer 1; its copy of layer 2, which
+// second_mask reads, is replaced with the device's.  kh_bsgs_save would write these bits (or rebuild a
+// blocked layer 1), so it refuses until the next kh_bsgs_build / _load.
 int kh_bsgs_set_bloom(kh_ctx *ctx, uint32_t layer, const uint8_t *buf, uint64_t bytes) {
   if (!ctx || !buf) return KH_E_ARG;
   if (!ctx->bsgs_built) return KH_E_STATE;
-  const bloom_desc &d = ctx->bd[0];
-  if (layer != 1 || bytes != 256 * d.bytes) {
-    ctx->err = "kh_bsgs_set_bloom takes layer 1 and kh_get_bloom's byte count (" + std::to_string(256 * d.bytes) + ")";
+  if (layer != 1 && layer != 2) {
+    ctx->err = "kh_bsgs_set_bloom takes layer 1 or 2";
+    return KH_E_ARG;
+  }
+  const bloom_desc &d = ctx->bd[layer - 1];
+  if (bytes != 256 * d.bytes) {
+    ctx->err = "kh_bsgs_set_bloom takes kh_get_bloom's byte count (" + std::to_string(256 * d.bytes) + ")";
     return KH_E_ARG;
   }
   (void)hipSetDevice(ctx->device);
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  HIPCHK(ctx, hipMemcpy2D(ctx->d_bl[0].get(), d.stride, buf, d.bytes, d.bytes, 256, hipMemcpyHostToDevice));
-  ctx->l1_replaced = true;
+  if (ctx->side) HIPCHK(ctx, hipStreamSynchronize(ctx->side));
+  HIPCHK(ctx, hipMemcpy2D(ctx->d_bl[layer - 1].get(), d.stride, buf, d.bytes, d.bytes, 256, hipMemcpyHostToDevice));
+  if (layer == 2) {
+    std::vector<uint8_t> &h = ctx->h_bl[1];
+    h.assign(256 * d.stride, 0);
+    for (int i = 0; i < 256; i++) memcpy(&h[(size_t)i * d.stride], buf + (size_t)i * d.bytes, d.bytes);
+  }
+  ctx->layer_replaced = true;
   return KH_OK;
 }
 

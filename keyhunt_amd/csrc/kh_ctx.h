@@ -112,7 +112,7 @@ struct kh_ctx {
   uint32_t l1_layout = KH_LAYER1_BLOCKED;
   uint32_t bloom_mult = 1;   // -z (FLAGBLOOMMULTIPLIER) for the BSGS shards, kh_bsgs_set_bloom_multiplier
   bool bsgs_ready = false, bsgs_built = false;
-  bool l1_replaced = false;  // kh_bsgs_set_bloom put a test's layer 1 on the device: kh_bsgs_save refuses
+  bool layer_replaced = false;  // kh_bsgs_set_bloom put a test's layer 1 or 2 in place: kh_bsgs_save refuses
   kh_bsgs_info info{};
   bloom_desc bd[3]{};
   bloom_desc bd_ref1{};      // layer 1 in the reference layout (what its files hold)

@@ -778,7 +778,9 @@ KH_HD void gej_to_ge(ge &r, const gej &p) {
   fe_mul(r.x, p.x, zi2);
   fe_mul(r.y, p.y, zi3);
 }
-// affine r = p + q with its own inversion (AddDirect, SECP256K1.cpp:455-478); p != +-q.
+// affine r = p + q with its own inversion: AddDirect(p, q) (SECP256K1.cpp:455-478) term by term, y taken
+// from the second operand as there.  For p.x == q.x the inverse of 0 counts as 0 (fe_inv), so s = 0 and
+// r = (-p.x - q.x, -q.y): the value the second check's dx = 0 branches reproduce.
 KH_HD void ge_add(ge &r, const ge &p, const ge &q) {
   fe dx, dy, s, s2, t;
   fe_sub(dx, q.x, p.x);
@@ -789,9 +791,9 @@ KH_HD void ge_add(ge &r, const ge &p, const ge &q) {
   fe rx, ry;
   fe_sub(rx, s2, p.x);
   fe_sub(rx, rx, q.x);
-  fe_sub(t, p.x, rx);
+  fe_sub(t, q.x, rx);
   fe_mul(ry, s, t);
-  fe_sub(ry, ry, p.y);
+  fe_sub(ry, ry, q.y);
   r.x = rx;
   r.y = ry;
 }

@@ -48,6 +48,14 @@ class KhBsgsFound(ctypes.Structure):
     _fields_ = [("target", ctypes.c_uint32), ("pad", ctypes.c_uint32), ("key", ctypes.c_uint8 * 32)]
 
 
+class KhSetupForm(ctypes.Structure):
+    _fields_ = [("prog", ctypes.c_uint32), ("L", ctypes.c_uint32), ("scalars", ctypes.c_char_p),
+                ("s0", ctypes.c_uint8 * 32), ("step", ctypes.c_uint8 * 32), ("list", ctypes.c_char_p),
+                ("n_bases", ctypes.c_uint64), ("start", ctypes.c_uint8 * 32), ("t_round", ctypes.c_uint64),
+                ("lane_pts", ctypes.c_uint64), ("a_pts", ctypes.c_uint64), ("two_n", ctypes.c_uint64),
+                ("m", ctypes.c_uint64), ("h", ctypes.c_uint32)]
+
+
 class KhMinikeyHit(ctypes.Structure):
     _fields_ = [("key", ctypes.c_uint8 * 32), ("offset", ctypes.c_uint64), ("ordinal", ctypes.c_uint64),
                 ("minikey", ctypes.c_char * 24)]
@@ -114,6 +122,10 @@ def lib() -> ctypes.CDLL:
     L.kh_bsgs_refine_stats.argtypes = [P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.kh_bsgs_second_masks.argtypes = [P, ctypes.c_uint32, u8p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
                                        ctypes.POINTER(ctypes.c_uint32)]
+    L.kh_bsgs_refine_masks.argtypes = [P, ctypes.c_uint32, u8p, u8p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                       ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32,
+                                       ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+    L.kh_setup_centres.argtypes = [P, ctypes.POINTER(KhSetupForm), u8p, u8p]
     L.kh_kernel_time.argtypes = [P, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double),
                                  ctypes.POINTER(ctypes.c_uint64)]
     L.kh_kernel_time_reset.argtypes = [P]
@@ -403,6 +415,24 @@ class Engine:
         self._chk(lib().kh_bsgs_second_masks(self._ctx, target, buf, n, g, h), "kh_bsgs_second_masks")
         return list(g[:n]), list(h[:n])
 
+    def bsgs_refine_masks_status(self, target: int, idx: list[int], a_pts: int, t_round: int = 0, start: int = None,
+                                 two_n: int = 0, bases: list[int] = None, two_m: int = 0):
+        """kh_bsgs_refine_masks returning (status, GPU masks, host masks): k_refine over its own index
+        arithmetic, continuous (start, two_n) or list (bases) form; two_m = 0: the tables' 2M."""
+        n = len(idx)
+        g, h = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint32 * max(n, 1))()
+        lst = b"".join(be32(b) for b in bases) if bases is not None else None
+        r = lib().kh_bsgs_refine_masks(self._ctx, target, be32(start) if start is not None else None, lst,
+                                       len(bases) if bases is not None else 0, t_round, a_pts, two_n, two_m,
+                                       (ctypes.c_uint64 * max(n, 1))(*idx), n, g, h)
+        return r, list(g[:n]), list(h[:n])
+
+    def bsgs_refine_masks(self, target: int, idx: list[int], a_pts: int, t_round: int = 0, start: int = None,
+                          two_n: int = 0, bases: list[int] = None, two_m: int = 0) -> tuple[list[int], list[int]]:
+        r, g, h = self.bsgs_refine_masks_status(target, idx, a_pts, t_round, start, two_n, bases, two_m)
+        self._chk(r, "kh_bsgs_refine_masks")
+        return g, h
+
     # -- measurement ---------------------------------------------------------------------------
     def kernel_time(self, kind: int) -> tuple[int, float, int]:
         la, ms, pts = ctypes.c_uint64(), ctypes.c_double(), ctypes.c_uint64()
@@ -421,6 +451,41 @@ class Engine:
         raw = out.raw
         return [(int.from_bytes(raw[64 * i:64 * i + 32], "big"), int.from_bytes(raw[64 * i + 32:64 * i + 64], "big"))
                 for i in range(len(scalars))]
+
+    def setup_centres_status(self, L: int, scalars: list[int] = None, prog: tuple[int, int] = None,
+                             bsgs: dict = None, q: tuple[int, int] = None):
+        """kh_setup_centres returning (status, raw L x 64 bytes): k_setup's centres [Q +] s_g*G of L lanes.
+        Exactly one form: scalars (prog 0), prog = (s0, step) (prog 1), or bsgs = dict(t_round, lane_pts,
+        a_pts, m, h and either start, two_n or bases) (prog 2)."""
+        f = KhSetupForm()
+        f.L = L
+        if scalars is not None:
+            f.prog = 0
+            f.scalars = b"".join(be32(s) for s in scalars)
+        elif prog is not None:
+            f.prog = 1
+            f.s0 = (ctypes.c_uint8 * 32)(*be32(prog[0]))
+            f.step = (ctypes.c_uint8 * 32)(*be32(prog[1]))
+        else:
+            f.prog = 2
+            if bsgs.get("bases") is not None:
+                f.list = b"".join(be32(b) for b in bsgs["bases"])
+                f.n_bases = len(bsgs["bases"])
+            f.start = (ctypes.c_uint8 * 32)(*be32(bsgs.get("start", 0)))
+            f.two_n = bsgs.get("two_n", 0)
+            f.t_round, f.lane_pts, f.a_pts = bsgs.get("t_round", 0), bsgs["lane_pts"], bsgs["a_pts"]
+            f.m, f.h = bsgs["m"], bsgs["h"]
+        out = ctypes.create_string_buffer(64 * max(L, 1))
+        qb = be32(q[0]) + be32(q[1]) if q is not None else None
+        r = lib().kh_setup_centres(self._ctx, ctypes.byref(f), qb, out)
+        return r, out.raw
+
+    def setup_centres(self, L: int, scalars: list[int] = None, prog: tuple[int, int] = None, bsgs: dict = None,
+                      q: tuple[int, int] = None) -> bytes:
+        """The centres as L x (x[32] || y[32]) big-endian bytes (see setup_centres_status)."""
+        r, raw = self.setup_centres_status(L, scalars, prog, bsgs, q)
+        self._chk(r, "kh_setup_centres")
+        return raw
 
     def walk_points(self, start: int, n_points: int, stride: int = 1, need_y: bool = False):
         xs = ctypes.create_string_buffer(32 * n_points)
@@ -499,7 +564,7 @@ class Engine:
         return buf.raw
 
     def set_bloom(self, layer: int, data: bytes) -> None:
-        """Parity hook: replace BSGS layer 1 on the device by `data` (get_bloom(1)'s size and layout)."""
+        """Parity hook: replace BSGS layer 1 or 2 by `data` (get_bloom(layer)'s size and layout)."""
         self._chk(lib().kh_bsgs_set_bloom(self._ctx, layer, data, len(data)), "kh_bsgs_set_bloom")
 
     def get_bsgs_table(self) -> bytes:

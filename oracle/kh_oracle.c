@@ -626,6 +626,15 @@ int or_point_add(const uint8_t ax[32], const uint8_t ay[32], const uint8_t bx[32
   fe_to_be(rx, &r.x); fe_to_be(ry, &r.y);
   return r.inf;
 }
+/* Secp256K1::AddDirect itself (ge_add_direct): no special cases, the inverse of dx = 0 taken as 0 */
+void or_add_direct(const uint8_t ax[32], const uint8_t ay[32], const uint8_t bx[32], const uint8_t by[32],
+                   uint8_t rx[32], uint8_t ry[32]) {
+  ge a, b, r;
+  fe_from_be(&a.x, ax); fe_from_be(&a.y, ay); a.inf = 0;
+  fe_from_be(&b.x, bx); fe_from_be(&b.y, by); b.inf = 0;
+  ge_add_direct(&r, &a, &b);
+  fe_to_be(rx, &r.x); fe_to_be(ry, &r.y);
+}
 
 /* ------------------------------------------------------------------------------------------ */
 /* The reference's 1024-point group walk (keyhunt.cpp:3349-3461 + IntGroup.cpp:36-58).         */

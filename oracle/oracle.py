@@ -97,6 +97,15 @@ def point_add(a: tuple[int, int], b: tuple[int, int]) -> tuple[int, int]:
     return int.from_bytes(rx.raw, "big"), int.from_bytes(ry.raw, "big")
 
 
+def add_direct(a: tuple[int, int], b: tuple[int, int]) -> tuple[int, int]:
+    """Secp256K1::AddDirect(a, b) (SECP256K1.cpp:455-478) as kh_oracle.c restates it (ge_add_direct): the
+    chord formula with no special cases; where a.x == b.x the inverse of 0 counts as 0."""
+    rx = ctypes.create_string_buffer(32)
+    ry = ctypes.create_string_buffer(32)
+    lib().or_add_direct(be32(a[0]), be32(a[1]), be32(b[0]), be32(b[1]), rx, ry)
+    return int.from_bytes(rx.raw, "big"), int.from_bytes(ry.raw, "big")
+
+
 def hash160_comp(x: int, prefix: int) -> bytes:
     out = ctypes.create_string_buffer(20)
     lib().or_hash160_comp(be32(x), ctypes.c_uint8(prefix), out)

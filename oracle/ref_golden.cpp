@@ -292,6 +292,27 @@ int main() {
                (unsigned long long)a, (unsigned long long)b, len == 32 && t == 3 ? "" : ",");
       }
   }
+  printf("],\n");
+  // ---------------- AddDirect where dx = 0 (ModInv of 0 leaves 0) ----------------
+  // Emitted last and from fixed keys, so every key above stays byte-identical.  Per key k, P = k*G:
+  // AddDirect(P, P), AddDirect(P, -P) and, as bsgs_secondcheck calls it for a base key equal to the
+  // target's key (keyhunt.cpp:5171), AddDirect(Q, -k*G) with Q = k*G taken as a point of its own.
+  printf("\"add_direct_dx0\": [\n");
+  {
+    const char *dk[] = {"1", "7CCE5EFDACCF6808", "33E7665705359F04F28B88CF897C603C9"};
+    for (int t = 0; t < 3; t++) {
+      Int k; k.SetBase16((char *)dk[t]);
+      Point Pt = secp->ComputePublicKey(&k);
+      Point Ng = secp->Negation(Pt);
+      Point Q = secp->ComputePublicKey(&k);
+      Point pp = secp->AddDirect(Pt, Pt);
+      Point pn = secp->AddDirect(Pt, Ng);
+      Point qn = secp->AddDirect(Q, Ng);
+      printf("  {\"k\":\"%s\",\"x\":\"%s\",\"y\":\"%s\",\"pp\":[\"%s\",\"%s\"],\"pn\":[\"%s\",\"%s\"],\"qn\":[\"%s\",\"%s\"]}%s\n",
+             ihex(k).c_str(), ihex(Pt.x).c_str(), ihex(Pt.y).c_str(), ihex(pp.x).c_str(), ihex(pp.y).c_str(),
+             ihex(pn.x).c_str(), ihex(pn.y).c_str(), ihex(qn.x).c_str(), ihex(qn.y).c_str(), t == 2 ? "" : ",");
+    }
+  }
   printf("]\n}\n");
   return 0;
 }

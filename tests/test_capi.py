@@ -49,6 +49,20 @@ def test_null_context_is_rejected():
     assert L.kh_open(0, None) == -1
 
 
+def test_kernel_hooks_reject_null_arguments():
+    """kh_setup_centres, kh_bsgs_refine_masks and kh_bsgs_set_bloom refuse a null context (the one
+    refusal that needs no device; the others are checked on a context in test_gpu_setup_refine.py)."""
+    L = keyhunt_amd.lib()
+    f = E.KhSetupForm()
+    f.L = 1
+    out = ctypes.create_string_buffer(64)
+    assert L.kh_setup_centres(None, ctypes.byref(f), None, out) == -1
+    idx, g, h = (ctypes.c_uint64 * 1)(0), (ctypes.c_uint32 * 1)(), (ctypes.c_uint32 * 1)()
+    assert L.kh_bsgs_refine_masks(None, 0, b"\0" * 32, None, 0, 0, 1, 2, 0, idx, 1, g, h) == -1
+    assert L.kh_bsgs_set_bloom(None, 2, b"\0" * 16, 16) == -1
+    assert {"kh_setup_centres", "kh_bsgs_refine_masks"} <= set(keyhunt_amd.header_symbols())
+
+
 def test_device_count_without_gpu_is_zero_or_more():
     assert keyhunt_amd.device_count() >= 0
 

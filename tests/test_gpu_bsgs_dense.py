@@ -357,8 +357,8 @@ def test_overflow_grows_and_redoes(dense, oracle):
 
 
 def test_set_bloom_argument_and_state_errors(oracle, tmp_path):
-    """kh_bsgs_set_bloom: KH_E_STATE before the tables exist, KH_E_ARG for another layer or byte count;
-    kh_bsgs_save refuses after it until the tables are built again."""
+    """kh_bsgs_set_bloom: KH_E_STATE before the tables exist, KH_E_ARG for a layer other than 1 and 2 or
+    another byte count; kh_bsgs_save refuses after either layer until the tables are built again."""
     import keyhunt_amd as K
     KH_E_ARG = -1
     with K.Engine(0, LANES, 0) as e:
@@ -368,10 +368,15 @@ def test_set_bloom_argument_and_state_errors(oracle, tmp_path):
         assert status(1, bytes(16)) == K.KH_E_STATE
         e.bsgs_build()
         l1 = e.get_bloom(1)
-        for layer, data in ((2, e.get_bloom(2)), (0, l1), (3, l1), (1, l1[:-1]), (1, l1 + b"\0")):
+        l2, l3 = e.get_bloom(2), e.get_bloom(3)
+        for layer, data in ((0, l1), (3, l1), (3, l3), (4, l1), (1, l1[:-1]), (1, l1 + b"\0"), (2, l2[:-1]),
+                            (2, l2 + b"\0")):
             assert status(layer, data) == KH_E_ARG, (layer, len(data))
-        assert e.get_bloom(1) == l1
+        assert (e.get_bloom(1), e.get_bloom(2), e.get_bloom(3)) == (l1, l2, l3)
         e.set_bloom(1, l1)
+        assert K.lib().kh_bsgs_save(e._ctx, str(tmp_path).encode()) == K.KH_E_STATE
+        e.bsgs_build()
+        e.set_bloom(2, l2)                               # layer 2 is taken too, and save refuses as well
         assert K.lib().kh_bsgs_save(e._ctx, str(tmp_path).encode()) == K.KH_E_STATE
         e.bsgs_build()
         e.bsgs_save(str(tmp_path))
