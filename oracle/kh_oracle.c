@@ -781,15 +781,24 @@ static void push_hit(or_hit *hits, int cap, int *nh, const fe *k, int compressed
 
 /* thread_process for one chunk (keyhunt.cpp:3349-3830): per point, the compressed variants, then
  * the uncompressed ones; with endo (-e) each over the images e = 0, 1, 2 (beta^e * X), the 04
- * variants also over (X, -Y).  Kinds: base (0: 02, 1: 03, 2: 04, 3: xpoint) | e << 4 | neg << 6.
+ * variants also over (X, -Y).  Kinds: base (0: 02, 1: 03, 2: 04, 3: xpoint, 5: eth) | e << 4 |
+ * neg << 6.  -c eth with -e has six slots of its own (below).
  * scan_groups does groups [g0, g1) of the chunk into its own hit list. */
 typedef struct {
   int mode, search, endo, grp;  /* grp: keys per group (1024, or --rmd-batch-size) */
-  fe start;
+  fe start, stride;             /* -I: slot t of the chunk is the key start + t * stride */
   uint64_t g0, g1;
   const uint8_t *rows; int64_t n_rows; const uint8_t *bf; uint64_t bits; uint32_t hashes;
   or_hit *hits; int cap, nh;
 } scan_job;
+
+/* r = k + m * stride: the reference's plain Int sum for stride 1, mod n otherwise */
+static void slot_key(fe *r, const fe *k, const fe *stride, int unit, uint64_t m) {
+  if (unit) { u256_add_u64(r, k, m); return; }
+  fe mm = {{m, 0, 0, 0}}, d;
+  sc_mul(&d, &mm, stride);
+  sc_add(r, k, &d);
+}
 
 static void *scan_groups(void *arg) {
   scan_job *J = (scan_job *)arg;
@@ -804,16 +813,22 @@ static void *scan_groups(void *arg) {
   int need_y = (search == 1 || search == 2 || mode == 2);
   int ne = endo ? 3 : 1;
   const int grp = J->grp;
-  fe key, one = {{1, 0, 0, 0}};
-  u256_add_u64(&key, &J->start, J->g0 * (uint64_t)grp);
+  /* stride 1 keeps the reference's unreduced key_mpz (a chunk may run past the order); any other
+   * stride advances the keys mod n, as the engine does (far below the order the two agree) */
+  const fe one = {{1, 0, 0, 0}};
+  const fe stride = J->stride;
+  const int unit = u256_cmp(&stride, &one) == 0;
+  fe key = J->start;
+  if (!unit && u256_cmp(&key, &SC_N) >= 0) u256_sub(&key, &key, &SC_N);
+  slot_key(&key, &key, &stride, unit, J->g0 * (uint64_t)grp);
   walk_tab *wt = (walk_tab *)malloc(sizeof(walk_tab));
-  build_walk_tab(wt, &one);
+  build_walk_tab(wt, &stride);
   ge *pts = (ge *)malloc(sizeof(ge) * GRP);
   uint8_t *xs = (uint8_t *)malloc(GRP * 32), *ys = (uint8_t *)malloc(GRP * 32);
   for (uint64_t g = J->g0; g < J->g1; g++) {
     /* the centre from its key (keyhunt.cpp:3349-3353), then the group's points */
     fe ck; ge c;
-    u256_add_u64(&ck, &key, (uint64_t)(grp / 2));
+    slot_key(&ck, &key, &stride, unit, (uint64_t)(grp / 2));
     scalar_mult_g(&c, &ck);
     walk_group_n(wt, &c, pts, need_y, 0, grp / 2);
     for (int t = 0; t < grp; t++) {
@@ -821,16 +836,44 @@ static void *scan_groups(void *arg) {
       fe_to_be(ys + t * 32, &pts[t].y);
     }
     for (int t = 0; t < grp; t++) {
-      fe kf; u256_add_u64(&kf, &key, (uint64_t)t);
+      fe kf; slot_key(&kf, &key, &stride, unit, (uint64_t)t);  /* keyfound = t * stride + key_mpz */
       fe x0; fe_from_be(&x0, xs + t * 32);
       uint8_t xe[3][32];
       for (int e = 0; e < ne; e++) { fe v; fe_mul(&v, &x0, &END_BETA[e]); fe_to_be(xe[e], &v); }
-      if (mode == 2) {  /* -c eth (keyhunt.cpp:3524-3548, 3703-3760): the uncompressed point */
+      if (mode == 2 && !endo) {  /* -c eth (keyhunt.cpp:3538-3542, 3751-3764): the uncompressed point */
         uint8_t ya[32], h[20];
         memcpy(ya, ys + t * 32, 32);
         or_eth_address(xs + t * 32, ya, h);
         if (or_bloom_check(bf, bits, hashes, h, 20) && or_searchbinary(rows, n_rows, h, 20, 0))
           push_hit(hits, cap, &nh, &kf, 0, 5);
+        continue;
+      }
+      if (mode == 2) {
+        /* -c eth -e (keyhunt.cpp:3524-3536): six slots per point, eth of P, -P, beta P, -beta P,
+           beta P AGAIN (slot 4 passes endomorphism_beta where beta2 is meant) and -beta^2 P.  A hit
+           in slot l takes the slot key times lambda^(l/2), and is negated when the eth address of
+           that key's own public key is not the matched image (3714-3744) -- so always in slot 4,
+           and at every slot whose point is no multiple of G (groups below 1024).  Kinds as the
+           engine reports them: 5 | e << 4 | neg << 6 with e = l / 2, slot 4 being 5 | 2 << 4. */
+        static const int SLOT_E[6] = {0, 0, 1, 1, 1, 2};
+        fe y0; fe_from_be(&y0, ys + t * 32);
+        fe ny; fe_neg(&ny, &y0);
+        uint8_t yb[2][32];
+        fe_to_be(yb[0], &y0); fe_to_be(yb[1], &ny);
+        for (int l = 0; l < 6; l++) {
+          uint8_t h[20];
+          or_eth_address(xe[SLOT_E[l]], yb[l % 2], h);
+          if (or_bloom_check(bf, bits, hashes, h, 20) && or_searchbinary(rows, n_rows, h, 20, 0)) {
+            fe kr = kf;
+            if (l >= 2) sc_mul(&kr, &kf, &END_LAMBDA[l / 2]);
+            ge P; scalar_mult_g(&P, &kr);
+            uint8_t px[32], py[32], h2[20];
+            fe_to_be(px, &P.x); fe_to_be(py, &P.y);
+            or_eth_address(px, py, h2);
+            if (memcmp(h2, h, 20) != 0) sc_neg(&kr, &kr);
+            push_hit(hits, cap, &nh, &kr, 0, 5 | ((l / 2) << 4) | ((l % 2) << 6));
+          }
+        }
         continue;
       }
       if (mode == 1) {  /* xpoint (keyhunt.cpp:3801-3824) */
@@ -888,7 +931,7 @@ static void *scan_groups(void *arg) {
         }
       }
     }
-    u256_add_u64(&key, &key, (uint64_t)grp);
+    slot_key(&key, &key, &stride, unit, (uint64_t)grp);
   }
   free(xs); free(ys); free(pts); free(wt);
   J->nh = nh;
@@ -898,10 +941,16 @@ static void *scan_groups(void *arg) {
 /* the chunk on up to 16 threads (contiguous group ranges, hits concatenated in key order) */
 /* grp: keys per group -- 1024, or -m rmd160 --rmd-batch-size (a multiple of 4 below 1024): the
  * chunk is then ceil(n_keys / grp) whole groups (the reference's do-while, keyhunt.cpp:3350-3836) */
-int or_scan_chunk3(int mode, int search, int endo, int grp, const uint8_t start_be[32], uint64_t n_keys,
+/* stride_be: -I (keyhunt.cpp:1195-1207): slot t holds the key start + t * stride; the walk table is
+ * Gn[i] = (i+1) * stride * G (5267) and centres come from their keys (3349-3353) */
+int or_scan_chunk4(int mode, int search, int endo, int grp, const uint8_t start_be[32],
+                   const uint8_t stride_be[32], uint64_t n_keys,
                    const uint8_t *rows, int64_t n_rows, const uint8_t *bf, uint64_t bits, uint32_t hashes,
                    or_hit *hits, int cap) {
   if (grp < 4 || grp > GRP || grp % 4) return -1;
+  fe stride;
+  fe_from_be(&stride, stride_be);
+  if (u256_is_zero(&stride) || u256_cmp(&stride, &SC_N) >= 0) return -1;
   uint64_t groups = (n_keys + grp - 1) / grp;
   int nt = (int)(groups < 16 ? (groups ? groups : 1) : 16);
   scan_job *jobs = (scan_job *)calloc(nt, sizeof(scan_job));
@@ -910,6 +959,7 @@ int or_scan_chunk3(int mode, int search, int endo, int grp, const uint8_t start_
     scan_job *J = &jobs[i];
     J->mode = mode; J->search = search; J->endo = endo; J->grp = grp;
     fe_from_be(&J->start, start_be);
+    J->stride = stride;
     J->g0 = groups * i / nt; J->g1 = groups * (i + 1) / nt;
     J->rows = rows; J->n_rows = n_rows; J->bf = bf; J->bits = bits; J->hashes = hashes;
     J->cap = cap; J->hits = (or_hit *)calloc(cap > 0 ? cap : 1, sizeof(or_hit));
@@ -926,6 +976,14 @@ int or_scan_chunk3(int mode, int search, int endo, int grp, const uint8_t start_
   }
   free(jobs); free(th);
   return nh;
+}
+
+int or_scan_chunk3(int mode, int search, int endo, int grp, const uint8_t start_be[32], uint64_t n_keys,
+                   const uint8_t *rows, int64_t n_rows, const uint8_t *bf, uint64_t bits, uint32_t hashes,
+                   or_hit *hits, int cap) {
+  uint8_t one_be[32] = {0};
+  one_be[31] = 1;
+  return or_scan_chunk4(mode, search, endo, grp, start_be, one_be, n_keys, rows, n_rows, bf, bits, hashes, hits, cap);
 }
 
 int or_scan_chunk2(int mode, int search, int endo, const uint8_t start_be[32], uint64_t n_keys,

@@ -122,6 +122,12 @@ E2E_RUNS = [
     ("rmd160_batch1001_compress_endo", ["-m", "rmd160", "-f", "rmd_batch.rmd", "-l", "compress", "-e", "--rmd-batch-size", "1001", "-r", "10000:20ffff", "-n", "0x100000", "-t", "8"], 300),
     ("rmd160_batch1024_both", ["-m", "rmd160", "-f", "rmd_batch.rmd", "-l", "both", "--rmd-batch-size", "1024", "-r", "10000:20ffff", "-n", "0x100000", "-t", "8"], 300),
     ("rmd160_eth_batch8", ["-m", "rmd160", "-c", "eth", "-f", "eth_targets.rmd", "--rmd-batch-size", "8", "-r", "1:100000", "-n", "0x100000", "-t", "8"], 300),
+    # -c eth -e in groups below 1024: the six eth slots over each group's one real point and its
+    # G - 1 degenerate ones, and -I with -e (tests/golden/make_eth_endo_batch_targets.py); one thread,
+    # so the record order is pinned too (ORDERED)
+    ("rmd160_eth_endo_batch8_t1", ["-m", "rmd160", "-c", "eth", "-e", "-f", "eth_endo_batch8.rmd", "--rmd-batch-size", "8", "-r", "1:100000", "-n", "0x100000", "-t", "1"], 300),
+    ("rmd160_eth_endo_batch512_t1", ["-m", "rmd160", "-c", "eth", "-e", "-f", "eth_endo_batch512.rmd", "--rmd-batch-size", "512", "-r", "1:100000", "-n", "0x100000", "-t", "1"], 300),
+    ("address_endo_stride_t1", ["-m", "address", "-l", "both", "-e", "-I", "7919", "-f", "endo_stride.txt", "-r", "1:100000", "-n", "0x100000", "-t", "1"], 300),
     # no range at all: sequential from 1 (keyhunt.cpp:1250-1255)
     ("address_1to32_no_range", ["-m", "address", "-f", "1to32.txt", "-l", "compress", "-n", "0x100000", "-t", "8"], 20),
 ]
@@ -260,7 +266,8 @@ STDOUT_NOTE = re.compile(r"^(?:ParsePublicKeyHex: |Invalid length: )[^\n]*$", re
 
 
 # single-thread runs whose KEYFOUNDKEYFOUND.txt record order is pinned too ("hits_in_order")
-ORDERED = {"address_eth_endo_pair_t1"}
+ORDERED = {"address_eth_endo_pair_t1", "rmd160_eth_endo_batch8_t1", "rmd160_eth_endo_batch512_t1",
+           "address_endo_stride_t1"}
 
 
 def gen_e2e(only: list[str] | None = None) -> None:

@@ -209,21 +209,24 @@ SEARCH_COMPRESS, SEARCH_UNCOMPRESS, SEARCH_BOTH = 0, 1, 2
 
 
 def scan_chunk(mode: int, search: int, start: int, n_keys: int, rows: list[bytes], cap: int = 4096,
-               endo: bool = False, group: int = 1024):
+               endo: bool = False, group: int = 1024, stride: int = 1):
     """Reference hit list for one chunk (thread_process).  rows: 20-byte targets (unsorted ok).
-    endo: -e (kinds then carry the image e << 4 and, for 04 hashes, the Y sign << 6).  group:
-    -m rmd160 --rmd-batch-size after the reference's clamping (kh_oracle.c walk_group_n)."""
+    endo: -e (kinds then carry the image e << 4 and, for 04 and eth hashes, the Y sign << 6; -c eth
+    reports its repeated slot 4 as 5 | 2 << 4).  group: -m rmd160 --rmd-batch-size after the
+    reference's clamping (kh_oracle.c walk_group_n).  stride: -I, slot t is the key start + t * stride."""
     srt = sorted(rows)
     table = b"".join(srt)
     bloom = Bloom(len(srt))
     for r in srt:
         bloom.add(r)
     hits = (OrHit * cap)()
-    n = lib().or_scan_chunk3(ctypes.c_int(mode), ctypes.c_int(search), ctypes.c_int(1 if endo else 0),
-                             ctypes.c_int(group), be32(start),
+    n = lib().or_scan_chunk4(ctypes.c_int(mode), ctypes.c_int(search), ctypes.c_int(1 if endo else 0),
+                             ctypes.c_int(group), be32(start), be32(stride),
                              ctypes.c_uint64(n_keys),
                             table, ctypes.c_int64(len(srt)), bloom.bf, ctypes.c_uint64(bloom.bits),
                             ctypes.c_uint32(bloom.hashes), hits, ctypes.c_int(cap))
+    if n < 0:
+        raise ValueError("bad group size or stride")
     return [(int.from_bytes(bytes(h.key), "big"), bool(h.compressed), int(h.kind)) for h in hits[: min(n, cap)]]
 
 

@@ -146,6 +146,121 @@ def test_oracle_rmd_batch_vs_reference_cli(oracle, name, search, endo, group):
     assert [f"{k:x}" for k in sorted(keys)] == [x["key"] for x in E2E[name]["hits"]]
 
 
+def _keys_vs_fixture(name, hits):
+    """The oracle's keys equal the fixture's as a sorted list; for a one-thread fixture
+    ("hits_in_order") the oracle's own order is the reference's record order too."""
+    ref = E2E[name]
+    assert ref["exit"] == 0
+    assert [f"{k:x}" for k in sorted(k for k, _, _ in hits)] == [x["key"] for x in ref["hits"]]
+    if "hits_in_order" in ref:
+        assert [f"{k:x}" for k, _, _ in hits] == [x["key"] for x in ref["hits_in_order"]]
+
+
+@pytest.mark.parametrize("name,fn", [
+    ("address_eth_2p20_endo", "eth_targets.txt"),
+    ("address_eth_endo_2p20", "eth_endo.txt"),
+    ("address_eth_endo_pair_t1", "eth_endo_pair.txt"),
+])
+def test_oracle_eth_endo_vs_reference_cli(oracle, name, fn):
+    """-c eth -e over 1..2^20: the oracle's six slots per point (keyhunt.cpp:3524-3536, slot 4 the
+    beta image again) and its per-slot keys (3714-3744) give the reference CLI's records; for the
+    one-thread pair fixture also in its order (the slot-4 record between slots 3 and 5)."""
+    from conftest import DATA
+    rows = [bytes.fromhex(s.strip()[-40:]) for s in open(os.path.join(DATA, fn)) if len(s.strip()) in (40, 42)]
+    hits = oracle.scan_chunk(oracle.MODE_ETH, 2, 1, 1 << 20, rows, endo=True)
+    assert all(c is False and kind & 15 == 5 for _, c, kind in hits)
+    if name == "address_eth_endo_pair_t1":
+        assert "hits_in_order" in E2E[name]
+        # key 9999: slots 2, 3 and the slot-4 twin; key 77777: slots 2, 4 and 5
+        assert [kind for _, _, kind in hits] == [0x15, 0x55, 0x25, 0x15, 0x25, 0x65]
+    _keys_vs_fixture(name, hits)
+
+
+@pytest.mark.parametrize("name,fn,group,n_hits", [
+    ("rmd160_eth_endo_batch8_t1", "eth_endo_batch8.rmd", 8, 51),
+    ("rmd160_eth_endo_batch512_t1", "eth_endo_batch512.rmd", 512, 14),
+])
+def test_oracle_eth_endo_rmd_batch_vs_reference_cli(oracle, name, fn, group, n_hits):
+    """-m rmd160 -c eth -e --rmd-batch-size G over 1..2^20 on one thread: the reference ran these argv
+    (exit 0) and its records, in order, are the oracle's -- centres and degenerate slots (both sides of
+    a centre, slot 0, the last slot) under each of the five distinct images, the six records of a
+    centre whose five images are all targets, and nothing for a (beta^2 x, +y) row
+    (tests/golden/make_eth_endo_batch_targets.py)."""
+    argv = E2E[name]["argv"]
+    assert argv[argv.index("--rmd-batch-size") + 1] == str(group) and argv[argv.index("-t") + 1] == "1"
+    assert "hits_in_order" in E2E[name] and len(E2E[name]["hits"]) == n_hits
+    rows = _read_rows(oracle, fn, "addr")
+    hits = oracle.scan_chunk(oracle.MODE_ETH, 2, 1, 1 << 20, rows, endo=True, group=group)
+    _keys_vs_fixture(name, hits)
+    if group == 8:
+        # every slot kind occurs, and group 97's centre (key 1 + 97 * 8 + 4) gives six records in slot order
+        assert {kind for _, _, kind in hits} == {0x05, 0x45, 0x15, 0x55, 0x25, 0x65}
+        at = [i for i, (k, _, kind) in enumerate(hits) if (k, kind) == (1 + 97 * 8 + 4, 0x05)]
+        assert len(at) == 1
+        assert [kind for _, _, kind in hits[at[0]:at[0] + 6]] == [0x05, 0x45, 0x15, 0x55, 0x25, 0x65]
+    # without -e only the plain image is probed: a subset of the -e records
+    plain = oracle.scan_chunk(oracle.MODE_ETH, 2, 1, 1 << 20, rows, group=group)
+    assert plain and all(kind == 5 for _, _, kind in plain) and len(plain) < len(hits)
+
+
+def test_oracle_endo_stride_vs_reference_cli(oracle):
+    """-m address -l both -e -I 7919 over 2^20 slots from key 1 on one thread (the reference ran this
+    argv, exit 0): the oracle's stride path (walk table of multiples of 7919 G, slot keys 1 + 7919 t)
+    gives the reference's records in its order -- lambda and lambda^2 multiples and negations of slot
+    keys, 02/03 and 04; the key between two slots is not found."""
+    name = "address_endo_stride_t1"
+    argv = E2E[name]["argv"]
+    assert argv[argv.index("-I") + 1] == "7919" and "hits_in_order" in E2E[name]
+    rows = _read_rows(oracle, "endo_stride.txt", "addr")
+    assert len(rows) == 10
+    hits = oracle.scan_chunk(0, 2, 1, 1 << 20, rows, endo=True, stride=7919)
+    assert len(hits) == 9
+    _keys_vs_fixture(name, hits)
+    # stride 1 over keys 1..2^20 holds two of the planted keys: lambda * 1 and the one between two slots
+    lam = 0x5363AD4CC05C30E0A5261C028812645A122E22EA20816678DF02967C1B23BD72
+    assert [k for k, _, _ in oracle.scan_chunk(0, 2, 1, 1 << 20, rows, endo=True)] == [lam, 1 + 5 * 7919 + 1]
+
+
+@pytest.mark.parametrize("case", ["both_e", "eth_e"])
+def test_dense_endo_comparison_fails_on_a_wrong_hit_list(oracle, case):
+    """The comparison of tests/test_gpu_endo_dense.py (_endo_rows.check_hits), fed on the CPU: one group
+    with every slot a target under class offset mod C, and one point under every image.  The oracle's own
+    list (with each record's offset recovered from its key) passes; a list with one record's
+    image or sign bits swapped, one record dropped, two records of a point exchanged, or a negated key
+    fails."""
+    from collections import namedtuple
+    from _endo_rows import CASES, TWIN, check_hits, kind_of, plant
+    Hit = namedtuple("Hit", "key offset kind compressed")
+    mode, search, _, classes = CASES[case]
+    start, n, C = (1 << 65) + 12345, 1024, len(classes)
+    slots = [(t, oracle.pubkey(start + t), t % C) for t in range(n)]
+    rows, planted = plant(oracle, classes, slots)
+    rows += plant(oracle, classes, [(700, slots[700][1], None)])[0]  # one point under every image
+    rows = list(dict.fromkeys(rows))
+    planted += [(700, kind_of(c)) for c in classes]
+    ref = oracle.scan_chunk(mode, search, start, n, rows, cap=4 * n, endo=True)
+    kinds = [kind_of(c) for c in classes] + ([TWIN] if case == "eth_e" else [])
+    lam = 0x5363AD4CC05C30E0A5261C028812645A122E22EA20816678DF02967C1B23BD72
+    inv = [1, pow(lam, -1, oracle.SECP_N), pow(lam * lam, -1, oracle.SECP_N)]
+
+    def offset(key, kind):  # the slot key is +-key / lambda^e
+        return min((sign * key * inv[kind >> 4 & 3] - start) % oracle.SECP_N for sign in (1, -1))
+    good = [Hit(key, offset(key, kind), kind, comp) for key, comp, kind in ref]
+    assert [h.offset for h in good] == sorted(h.offset for h in good) and good[-1].offset == n - 1
+    assert len(good) == n + len(classes) - 1 + sum(1 for h in good if h.kind == TWIN)
+    check_hits(good, ref, planted, kinds)
+
+    def bad(i, **kw):
+        return good[:i] + [good[i]._replace(**kw)] + good[i + 1:]
+    i = next(j for j, h in enumerate(good) if h.offset == 700)
+    wrong = [bad(5, kind=good[5].kind ^ 0x10), bad(5, kind=good[5].kind ^ 0x30),
+             bad(i + 1, kind=good[i + 1].kind ^ 0x40), good[:300] + good[301:],
+             good[:i] + [good[i + 1], good[i]] + good[i + 2:], bad(9, key=oracle.SECP_N - good[9].key)]
+    for w in wrong:
+        with pytest.raises(AssertionError):
+            check_hits(w, ref, planted, kinds)
+
+
 def test_oracle_scan_window_66(oracle):
     rows = _read_rows(oracle, "66.rmd", "addr")
     start = 0x2832ED74F2B5E0000
