@@ -53,6 +53,12 @@ extern "C" {
                               slip at 3533) and -beta^2 P, each hit keyed as 3736-3744 derives it */
 #define KH_MODE_ENDO 0x10  /* OR into the mode: -e, also probe (beta*X, Y) and (beta^2*X, Y), i.e. keys
                               lambda*k and lambda^2*k (keyhunt.cpp:3408-3440, 3476-3830) */
+#define KH_MODE_P2SH 0x20  /* OR into KH_MODE_ADDRESS: segwit targets.  Each compressed digest h = hash160(02/03||X)
+                              is probed as without the flag, then its nested P2SH-P2WPKH (BIP-49) script hash
+                              hash160(00 14 || h) against the same rows: a row matches whichever digest equals
+                              it (a bech32 P2WPKH program is h itself).  KH_SEARCH_COMPRESS or _BOTH, with or
+                              without KH_MODE_ENDO, exact targets, no kh_set_rmd_batch group below 1024:
+                              anything else is KH_E_ARG.  The reference has no such mode. */
 #define KH_SEARCH_COMPRESS 0
 #define KH_SEARCH_UNCOMPRESS 1
 #define KH_SEARCH_BOTH 2   /* reference default (FLAGSEARCH = 2) */
@@ -74,6 +80,9 @@ extern "C" {
 #define KH_KIND_ENDO1 0x10 /* matched on (beta*X, Y): key = lambda*k (+- as reported) */
 #define KH_KIND_ENDO2 0x20 /* matched on (beta^2*X, Y): key = lambda^2*k */
 #define KH_KIND_NEGY 0x40  /* 04||X||-Y (or, -c eth, -Y) matched: key negated */
+/* with KH_MODE_P2SH, OR'ed into KH_KIND_02 / KH_KIND_03 (and the image bits): */
+#define KH_KIND_P2SH 0x80  /* hash160(00 14 || hash160(02/03||X)) matched; the key is the plain hit's.  Per
+                              point and image: plain 02, plain 03, nested 02, nested 03 */
 /* -e -c eth: ETH | ENDO2 without NEGY is the reference's repeated beta P image (slot 4), reported
    after its ETH | ENDO1 twin with key n - lambda^2 k, as the reference prints it */
 
@@ -313,6 +322,9 @@ int kh_bloom_check2(kh_ctx *ctx, uint32_t layer, const uint8_t *items, uint32_t 
  * interleaved pair form, hash160(04||X||Y), the Ethereum address -> 80 bytes.  Any (x, y) is hashed,
  * on the curve or not. */
 int kh_digests(kh_ctx *ctx, const uint8_t *xy, uint32_t n, uint8_t *out80);
+/* per input point, the nested digests as the KH_MODE_P2SH walks compute them (the pair form):
+ * hash160(00 14 || hash160(02||X)) and hash160(00 14 || hash160(03||X)) -> 40 bytes.  Any (x, y) is hashed. */
+int kh_digests_nested(kh_ctx *ctx, const uint8_t *xy, uint32_t n, uint8_t *out40);
 /* per 20-byte item, the filter key pair the walks derive from its first len (1..20) bytes:
  * ab[2i] = XXH64(item[0..len), bloom seed), ab[2i+1] = XXH64(item[0..len), ab[2i]) */
 int kh_filter_keys(kh_ctx *ctx, const uint8_t *items, uint32_t n, uint32_t len, uint64_t *ab);

@@ -528,7 +528,7 @@ int kh_set_vanity(kh_ctx *ctx, const uint8_t *ranges, uint64_t n, uint32_t probe
 int kh_scan_memory(uint64_t n_keys, uint32_t mode, uint32_t search, uint64_t *needed_bytes) {
   if (!needed_bytes || n_keys == 0) return KH_E_ARG;
   const bool endo = (mode & KH_MODE_ENDO) != 0;
-  mode &= ~(uint32_t)KH_MODE_ENDO;
+  mode &= ~(uint32_t)(KH_MODE_ENDO | KH_MODE_P2SH);  // the nested probes walk the plain form's geometry
   if (mode > KH_MODE_ETH || search > KH_SEARCH_BOTH) return KH_E_ARG;
   const int km = walk_mode(mode, search, endo);
   // kh_scan's choice at the default geometry (a chunk that reaches the order keeps the small groups,
@@ -548,9 +548,11 @@ int kh_scan_memory(uint64_t n_keys, uint32_t mode, uint32_t search, uint64_t *ne
 // the order one reference thread prints them: per point, compressed variants (image-major), then
 // uncompressed, then xpoint.
 static std::vector<kh_hit> resolve_hits(kh_ctx *ctx, uint32_t nd, const u256 &st, const u256 &stride, uint32_t mode,
-                                        bool endo, uint32_t zg, int H) {
-  auto order = [](uint32_t kind) {
+                                        bool endo, uint32_t zg, int H, bool p2sh = false) {
+  auto order = [p2sh](uint32_t kind) {
     uint32_t base = kind & 15u, e = (kind >> KH_DKIND_ENDO_SHIFT) & 3u, neg = (kind & KH_DKIND_NEG) ? 1u : 0u;
+    // KH_MODE_P2SH: per image plain 02, plain 03, nested 02, nested 03; the 04 hits follow as without it
+    if (p2sh) return base < 2 ? 4 * e + base + ((kind & KH_DKIND_P2SH) ? 2u : 0u) : 12 + 2 * e + neg;
     return base < 2 ? 2 * e + base : base == 2 || base == KH_KIND_ETH ? 6 + 2 * e + neg : 12 + e;
   };
   std::vector<kh_dev_hit> dh(ctx->h_hits.begin(), ctx->h_hits.begin() + nd);
@@ -611,6 +613,11 @@ static std::vector<kh_hit> resolve_hits(kh_ctx *ctx, uint32_t nd, const u256 &st
     bool compressed = false;
     if (base == KH_KIND_02 || base == KH_KIND_03) {
       hash160_comp(xe, 2 + base, w);
+      if (h.kind & KH_DKIND_P2SH) {  // the nested digest of that hash is what the filter matched
+        uint32_t hn[5];
+        hash160_nested(w, hn);
+        memcpy(w, hn, 20);
+      }
       compressed = true;
     } else if (base == KH_KIND_04) {
       hash160_uncomp(xe, ye, w);
@@ -663,8 +670,16 @@ int kh_scan(kh_ctx *ctx, const uint8_t start[32], const uint8_t stride_be[32], u
   const uint32_t zg = ctx->rmd_batch;
   if (!zg && n_keys % (2 * KH_WALK_H)) return KH_E_ARG;
   const bool endo = (mode & KH_MODE_ENDO) != 0;
-  mode &= ~(uint32_t)KH_MODE_ENDO;
+  const bool p2sh = (mode & KH_MODE_P2SH) != 0;
+  mode &= ~(uint32_t)(KH_MODE_ENDO | KH_MODE_P2SH);
   if (mode > KH_MODE_ETH || search > KH_SEARCH_BOTH) return KH_E_ARG;
+  if (p2sh && (mode != KH_MODE_ADDRESS || search == KH_SEARCH_UNCOMPRESS || ctx->vanity || zg)) {
+    ctx->err = mode != KH_MODE_ADDRESS           ? "KH_MODE_P2SH applies to KH_MODE_ADDRESS only (not xpoint, not eth)"
+               : search == KH_SEARCH_UNCOMPRESS ? "KH_MODE_P2SH needs compressed keys: a P2SH-P2WPKH key is compressed by rule"
+               : ctx->vanity                    ? "KH_MODE_P2SH needs exact targets, not vanity prefixes"
+                                                : "KH_MODE_P2SH does not walk --rmd-batch-size groups below 1024";
+    return KH_E_ARG;
+  }
   if (zg && (mode == KH_MODE_XPOINT || ctx->vanity)) {
     ctx->err = "--rmd-batch-size applies to -m rmd160 (hash160 or -c eth) with exact targets only";
     return KH_E_ARG;
@@ -697,7 +712,7 @@ int kh_scan(kh_ctx *ctx, const uint8_t start[32], const uint8_t stride_be[32], u
       return r0 == KH_E_OVERFLOW ? r0 : KH_E_RANGE;
     }
   }
-  const int km = walk_mode(mode, search, endo);
+  const int km = walk_mode(mode, search, endo) | (p2sh ? KM_P2SH : 0);
   u256 st = sc_reduce(u256_from_be(start));
   u256 stride = stride_be ? sc_reduce(u256_from_be(stride_be)) : u256_u64(1);
   if (u256_is_zero(stride)) return KH_E_ARG;
@@ -707,7 +722,7 @@ int kh_scan(kh_ctx *ctx, const uint8_t start[32], const uint8_t stride_be[32], u
   // -(i+1)*stride*G, whose zero difference collapses the group's batch inversion (parity note 4),
   // and only the reference's own geometry collapses the same groups (fixtures *_near_order)
   const int H = zg ? (int)(zg / 2)
-                : ((km == KM_XPOINT || km == KM_H160C) && n_keys % (2 * KH_WALK_HB) == 0 &&
+                : ((km == KM_XPOINT || (km & ~KM_P2SH) == KM_H160C) && n_keys % (2 * KH_WALK_HB) == 0 &&
                    !reaches_order(st, stride, n_keys + 4 * KH_WALK_HB) && !getenv("KH_NO_BIG_GROUPS"))
                     ? KH_WALK_HB
                     : KH_WALK_H;
@@ -785,7 +800,7 @@ int kh_scan(kh_ctx *ctx, const uint8_t start[32], const uint8_t stride_be[32], u
     ctx->cont_stride = stride;
     ctx->cont_next = sc_add(st, sc_mul_u128(stride, n_keys));
   }
-  const std::vector<kh_hit> out = resolve_hits(ctx, nd, st, stride, mode, endo, zg, H);
+  const std::vector<kh_hit> out = resolve_hits(ctx, nd, st, stride, mode, endo, zg, H, p2sh);
   *n_hits = (uint32_t)out.size();
   if (hits)
     for (uint32_t i = 0; i < out.size() && i < cap; i++) hits[i] = out[i];

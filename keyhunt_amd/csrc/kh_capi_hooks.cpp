@@ -471,6 +471,15 @@ int kh_digests(kh_ctx *ctx, const uint8_t *xy, uint32_t n, uint8_t *out80) {
   return KH_OK;
 }
 
+int kh_digests_nested(kh_ctx *ctx, const uint8_t *xy, uint32_t n, uint8_t *out40) {
+  if (!ctx || !xy || !out40 || !n) return KH_E_ARG;
+  (void)hipSetDevice(ctx->device);
+  std::vector<uint32_t> ho((size_t)n * 10);
+  KHTRY(run_pairs(ctx, fe_words(xy, 64, n), fe_words(xy + 32, 64, n), n, ho, launch_test_digests_nested));
+  memcpy(out40, ho.data(), (size_t)n * 40);
+  return KH_OK;
+}
+
 int kh_filter_keys(kh_ctx *ctx, const uint8_t *items, uint32_t n, uint32_t len, uint64_t *ab) {
   if (!ctx || !items || !ab || !n || len == 0 || len > 20) return KH_E_ARG;
   (void)hipSetDevice(ctx->device);

@@ -56,6 +56,13 @@ static_assert(KH_WALK_H >= 64 && KH_WALK_H <= 512 && (512 % KH_WALK_H) == 0,
 #ifndef KH_WALK_LB_HASH
 #define KH_WALK_LB_HASH 3
 #endif
+// KH_WALK_LB_P2SH: the blocked-filter KM_P2SH walk (k_walk<KM_H160CB | KM_P2SH>) at KH_WALK_LB_HASH's 3
+// waves/SIMD like every other KM_P2SH walk: at the plain compress walk's 4 it spills 55 VGPRs (224 B of
+// scratch per lane, against 12 and 52 B at 3) and measured 0.2-0.4 % slower (DESIGN.md 4 "Segwit targets",
+// profiles/segwit_rate_ab.json).
+#ifndef KH_WALK_LB_P2SH
+#define KH_WALK_LB_P2SH KH_WALK_LB_HASH
+#endif
 
 // Blocked layer-1 bloom (KH_LAYER1_BLOCKED), a split-block filter: per shard X[0], `blocks` 16-byte
 // blocks, blocks = ceil(KH_BLK_BITS_MUL x reference bits / 128).  An item X (an x-coordinate, so
@@ -166,6 +173,11 @@ KH_HD void kh_blk_masks(uint32_t s0, uint32_t s1, uint32_t s2, uint32_t m[4]) {
 #ifndef KH_H160_BLK
 #define KH_H160_BLK 1
 #endif
+//   KH_NESTED_PAIR the KM_P2SH walks nest a point's 02 and 03 digests together (hash160_nested2: the two
+//                SHA-256 blocks interleaved) instead of one after the other in the rolled prefix loop
+#ifndef KH_NESTED_PAIR
+#define KH_NESTED_PAIR 1
+#endif
 
 enum kh_walk_mode {
   KM_H160C = 0,   // hash160(02||X), hash160(03||X)          -l compress
@@ -183,11 +195,16 @@ enum kh_walk_mode {
   // flag on KM_H160C/U/B and KM_XPOINT: also probe the endomorphism images (beta*x, y) and
   // (beta^2*x, y), i.e. keys lambda*k and lambda^2*k (-e, keyhunt.cpp:3408-3440, 3476-3830)
   KM_ENDO = 16,
+  // flag on KM_H160C/B (and KM_H160CB): each plain compressed digest h is probed, then its nested
+  // P2SH-P2WPKH script hash hash160(00 14 || h) against the same filter (KH_MODE_P2SH)
+  KM_P2SH = 32,
 };
 // device hit kinds: base kind (0: 02||X, 1: 03||X, 2: 04||X||Y, 3: xpoint, 4: bsgs, 5: eth) plus, with
 // KM_ENDO, the image e (0: X, 1: beta*X, 2: beta^2*X) << 4 and, for 04 hashes, the Y sign << 6
 #define KH_DKIND_ENDO_SHIFT 4
 #define KH_DKIND_NEG 0x40u
+// KM_P2SH: the filter hit was the nested digest of the 02/03 hash (the ABI's KH_KIND_P2SH)
+#define KH_DKIND_P2SH 0x80u
 
 struct kh_dev_hit {
   uint64_t idx;   // point index within the job
@@ -334,6 +351,9 @@ hipError_t launch_test_bloom(const uint8_t *items, uint32_t n, uint32_t len, con
 // probe-path parity kernels: hash160_comp2 / hash160_uncomp / eth_address per point (20 words), the
 // filter key pair (a, b) of a digest's first len bytes, tblk_probe against the blocked target filter
 hipError_t launch_test_digests(const uint32_t *xs, const uint32_t *ys, uint32_t n, uint32_t *out, hipStream_t st);
+// per point the KM_P2SH walks' nested digests of hash160(02||X) and hash160(03||X) (10 words; ys unused)
+hipError_t launch_test_digests_nested(const uint32_t *xs, const uint32_t *ys, uint32_t n, uint32_t *out,
+                                      hipStream_t st);
 hipError_t launch_test_filter_keys(const uint8_t *items, uint32_t n, uint32_t len, uint64_t *out, hipStream_t st);
 hipError_t launch_test_tblk(const uint8_t *items, uint32_t n, const uint4 *tblk, uint32_t tblocks, uint32_t *out,
                             hipStream_t st);

@@ -212,8 +212,49 @@ __device__ __forceinline__ bool probe_h160(const walk_args &A, const uint32_t h[
   return bloom_probe_lazy(A.bloom, A.bd, a, [&](uint64_t s) { return xxh64_prefix(h, A.probe_len, s); });
 }
 
+// KM_P2SH: the nested digests hash160(00 14 || h) of a point's two plain digests against the filter
+// the plain ones were probed in; kinds 0/1 | KH_DKIND_P2SH | tag.  BLK: the blocked target filter only
+// (the filter reads words 0..2, so the nested RIPEMD-160's steps that feed only words 3..4 are dead)
+template <bool BLK>
+__device__ __forceinline__ void probe_nested(const walk_args &A, const uint32_t hh[2][5], uint64_t idx, uint32_t tag) {
+#if KH_NESTED_PAIR
+  uint32_t nn[2][5];
+  hash160_nested2(hh[0], hh[1], nn[0], nn[1]);
+#endif
+#pragma unroll 1
+  for (uint32_t k = 0; k < 2; k++) {
+    uint32_t n[5];
+#if KH_NESTED_PAIR
+#pragma unroll
+    for (int q = 0; q < 5; q++) n[q] = k ? nn[1][q] : nn[0][q];
+#else
+    uint32_t h[5];
+#pragma unroll
+    for (int q = 0; q < 5; q++) h[q] = k ? hh[1][q] : hh[0][q];
+    hash160_nested(h, n);
+#endif
+    if (BLK ? tblk_probe(A, n) : probe_h160(A, n)) record_hit(A, idx, k | KH_DKIND_P2SH | tag);
+  }
+}
+
 // hash160(02||X) and hash160(03||X) of one x-coordinate into the target bloom; kinds 0/1 | tag
+template <bool P2SH = false>
 __device__ __forceinline__ void probe_comp(const walk_args &A, const fe &x, uint64_t idx, uint32_t tag) {
+  if constexpr (P2SH) {
+    // each plain digest as without the flag, then the two nested ones: the device's order within a
+    // point does not matter (the host sorts), the digests do
+    uint32_t hh[2][5];
+    hash160_comp2(x, hh[0], hh[1]);
+#pragma unroll 1
+    for (uint32_t k = 0; k < 2; k++) {
+      uint32_t h[5];
+#pragma unroll
+      for (int q = 0; q < 5; q++) h[q] = k ? hh[1][q] : hh[0][q];
+      if (probe_h160(A, h)) record_hit(A, idx, k | tag);
+    }
+    probe_nested<false>(A, hh, idx, tag);
+    return;
+  }
 #if KH_HASH_PAIR
   uint32_t hh[2][5];
   hash160_comp2(x, hh[0], hh[1]);
@@ -277,7 +318,8 @@ __device__ __forceinline__ void probe_eth(const walk_args &A, const fe &x, const
 template <int MODE>
 __device__ __forceinline__ void probe_point(const walk_args &A, const fe &x, const fe &y, uint64_t idx) {
   if (idx >= A.n_points) return;
-  if constexpr (MODE == KM_H160CB) {
+  constexpr bool P2SH = (MODE & KM_P2SH) != 0;
+  if constexpr ((MODE & ~KM_P2SH) == KM_H160CB) {
     // hash160(02||X), hash160(03||X) against the blocked target filter only: the filter reads digest
     // words 0..2, so the RIPEMD-160 steps that feed only words 3..4 are dead code here
     uint32_t hh[2][5];
@@ -289,6 +331,7 @@ __device__ __forceinline__ void probe_point(const walk_args &A, const fe &x, con
       for (int q = 0; q < 5; q++) h[q] = k ? hh[1][q] : hh[0][q];
       if (tblk_probe(A, h)) record_hit(A, idx, k);
     }
+    if constexpr (P2SH) probe_nested<true>(A, hh, idx, 0);
     return;
   }
   if constexpr (MODE == KM_ETH) {
@@ -320,14 +363,14 @@ __device__ __forceinline__ void probe_point(const walk_args &A, const fe &x, con
     // images e = 0 (X), then with -e: 1 (beta*X) and 2 (beta^2*X); per point the reference
     // checks every compressed variant before the uncompressed ones (keyhunt.cpp:3476-3700)
     if constexpr (BASE == KM_H160C || BASE == KM_H160B) {
-      probe_comp(A, x, idx, 0);
+      probe_comp<P2SH>(A, x, idx, 0);
       if constexpr (ENDO) {
 #pragma unroll 1
         for (int e = 1; e <= 2; e++) {
           fe b, xe;
           endo_beta(b, e);
           fe_mul(xe, x, b);
-          probe_comp(A, xe, idx, (uint32_t)e << KH_DKIND_ENDO_SHIFT);
+          probe_comp<P2SH>(A, xe, idx, (uint32_t)e << KH_DKIND_ENDO_SHIFT);
         }
       }
     }
@@ -508,7 +551,8 @@ constexpr bool needs_y() {
 // 4 waves/SIMD even with a few spills; the hash160 modes prefer 3).
 template <int MODE>
 constexpr int walk_lb() {
-  return MODE == KM_H160CB ? KH_WALK_LB_H160CB
+  return MODE == (KM_H160CB | KM_P2SH) ? KH_WALK_LB_P2SH
+         : MODE == KM_H160CB ? KH_WALK_LB_H160CB
          : ((MODE & 15) == KM_H160C || (MODE & 15) == KM_H160U || (MODE & 15) == KM_H160B || (MODE & 15) == KM_ETH)
              ? KH_WALK_LB_HASH
          : MODE == KM_DUMP                                          ? 2
@@ -1421,6 +1465,19 @@ __global__ void k_test_digests(const uint32_t *xs, const uint32_t *ys, uint32_t 
   eth_address(x, y, o + 15);
 }
 
+// The KM_P2SH walks' nested digests of a point's two plain ones -> 10 words
+__global__ void k_test_digests_nested(const uint32_t *xs, const uint32_t *ys, uint32_t n, uint32_t *out) {
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  (void)ys;
+  fe x;
+  load_fe(x, xs + (size_t)i * 8);
+  uint32_t h02[5], h03[5];
+  hash160_comp2(x, h02, h03);
+  uint32_t *o = out + (size_t)i * 10;
+  hash160_nested2(h02, h03, o, o + 5);
+}
+
 // The filter key pair (a, b) of the first `len` (1..20) bytes of n 20-byte items, as probe_h160
 // derives it: xxh64_20 for the whole digest, xxh64_prefix for a vanity prefix.
 __global__ void k_test_filter_keys(const uint8_t *items, uint32_t n, uint32_t len, uint64_t *out) {
@@ -1550,6 +1607,7 @@ hipError_t launch_walk(int mode, const walk_args &A, hipStream_t st, int H) {
   dim3 block(256), grid((A.L + 255) / 256);
   if (KH_XPOINT_DEFER && mode == KM_XPOINT && A.tblk) mode = KM_XPOINTB;
   if (KH_H160_BLK && mode == KM_H160C && A.tblk) mode = KM_H160CB;
+  if (KH_H160_BLK && mode == (KM_H160C | KM_P2SH) && A.tblk) mode = KM_H160CB | KM_P2SH;
   if (H == KH_WALK_HB) {
     constexpr int TB = walk_threads<KM_BSGSB, KH_WALK_HB>();
     switch (mode) {
@@ -1561,6 +1619,12 @@ hipError_t launch_walk(int mode, const walk_args &A, hipStream_t st, int H) {
       case KM_XPOINTB: hipLaunchKernelGGL((k_walk<KM_XPOINTB, KH_WALK_HB>), grid, block, 0, st, A); break;
       case KM_H160C: hipLaunchKernelGGL((k_walk<KM_H160C, KH_WALK_HB>), grid, block, 0, st, A); break;
       case KM_H160CB: hipLaunchKernelGGL((k_walk<KM_H160CB, KH_WALK_HB>), grid, block, 0, st, A); break;
+      case KM_H160C | KM_P2SH:
+        hipLaunchKernelGGL((k_walk<KM_H160C | KM_P2SH, KH_WALK_HB>), grid, block, 0, st, A);
+        break;
+      case KM_H160CB | KM_P2SH:
+        hipLaunchKernelGGL((k_walk<KM_H160CB | KM_P2SH, KH_WALK_HB>), grid, block, 0, st, A);
+        break;
       default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -1589,6 +1653,15 @@ hipError_t launch_walk(int mode, const walk_args &A, hipStream_t st, int H) {
     case KM_H160B | KM_ENDO: hipLaunchKernelGGL(k_walk<KM_H160B | KM_ENDO>, grid, block, 0, st, A); break;
     case KM_XPOINT | KM_ENDO: hipLaunchKernelGGL(k_walk<KM_XPOINT | KM_ENDO>, grid, block, 0, st, A); break;
     case KM_ETH | KM_ENDO: hipLaunchKernelGGL(k_walk<KM_ETH | KM_ENDO>, grid, block, 0, st, A); break;
+    case KM_H160C | KM_P2SH: hipLaunchKernelGGL(k_walk<KM_H160C | KM_P2SH>, grid, block, 0, st, A); break;
+    case KM_H160CB | KM_P2SH: hipLaunchKernelGGL(k_walk<KM_H160CB | KM_P2SH>, grid, block, 0, st, A); break;
+    case KM_H160B | KM_P2SH: hipLaunchKernelGGL(k_walk<KM_H160B | KM_P2SH>, grid, block, 0, st, A); break;
+    case KM_H160C | KM_P2SH | KM_ENDO:
+      hipLaunchKernelGGL(k_walk<KM_H160C | KM_P2SH | KM_ENDO>, grid, block, 0, st, A);
+      break;
+    case KM_H160B | KM_P2SH | KM_ENDO:
+      hipLaunchKernelGGL(k_walk<KM_H160B | KM_P2SH | KM_ENDO>, grid, block, 0, st, A);
+      break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -1660,6 +1733,12 @@ hipError_t launch_test_bloom(const uint8_t *items, uint32_t n, uint32_t len, con
 
 hipError_t launch_test_digests(const uint32_t *xs, const uint32_t *ys, uint32_t n, uint32_t *out, hipStream_t st) {
   hipLaunchKernelGGL(k_test_digests, dim3((n + 127) / 128), dim3(128), 0, st, xs, ys, n, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_test_digests_nested(const uint32_t *xs, const uint32_t *ys, uint32_t n, uint32_t *out,
+                                      hipStream_t st) {
+  hipLaunchKernelGGL(k_test_digests_nested, dim3((n + 127) / 128), dim3(128), 0, st, xs, ys, n, out);
   return hipGetLastError();
 }
 

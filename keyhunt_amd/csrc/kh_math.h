@@ -1048,6 +1048,48 @@ KH_HD void hash160_comp2(const fe &x, uint32_t out02[5], uint32_t out03[5]) {
   ripemd160_32(m, out03);
 }
 
+// The P2SH-P2WPKH (BIP-49) script hash of a key hash: hash160(00 14 || h), the 22-byte redeem script
+// "push 0, push the 20-byte witness program".  h and out are 5 LE words, as ripemd160_32 writes them.
+// One SHA-256 block: with b_i = bswap32(h[i]) the words are 0x0014 | b0 >> 16, the b's shifted along by
+// 16 bits, b4 << 16 | 0x8000, zeros and the bit length 176; ten of the sixteen are constants.
+KH_HD void nested_block(const uint32_t h[5], uint32_t w[16]) {
+  uint32_t b[5];
+#pragma unroll
+  for (int i = 0; i < 5; i++) b[i] = bswap32(h[i]);
+  w[0] = 0x00140000u | (b[0] >> 16);
+#pragma unroll
+  for (int i = 1; i < 5; i++) w[i] = (b[i - 1] << 16) | (b[i] >> 16);
+  w[5] = (b[4] << 16) | 0x8000u;
+#pragma unroll
+  for (int i = 6; i < 15; i++) w[i] = 0;
+  w[15] = 0xB0u;
+}
+KH_HD void hash160_nested(const uint32_t h[5], uint32_t out[5]) {
+  uint32_t w[16], st[8], m[8];
+  nested_block(h, w);
+  sha256_init(st);
+  sha256_transform(st, w);
+#pragma unroll
+  for (int i = 0; i < 8; i++) m[i] = bswap32(st[i]);
+  ripemd160_32(m, out);
+}
+// Two of them with the SHA-256 compressions interleaved and the RIPEMD-160s one after the other, as
+// hash160_comp2 runs its pair: the nested digests of hash160(02||X) and hash160(03||X).
+KH_HD void hash160_nested2(const uint32_t ha[5], const uint32_t hb[5], uint32_t outa[5], uint32_t outb[5]) {
+  uint32_t wa[16], wb[16], sa[8], sb[8], m[8];
+  nested_block(ha, wa);
+  nested_block(hb, wb);
+  sha256_init(sa);
+  sha256_init(sb);
+  sha256_transform2(sa, wa, sb, wb);
+#pragma unroll
+  for (int i = 0; i < 8; i++) m[i] = bswap32(sa[i]);
+  ripemd160_32(m, outa);
+#pragma unroll
+  for (int i = 0; i < 8; i++) m[i] = bswap32(sb[i]);
+  ripemd160_32(m, outb);
+}
+
 // hash160(04 || X || Y) (KEYBUFFUNCOMP, secp256k1/SECP256K1.cpp:992-1024): two SHA-256 blocks.
 KH_HD void hash160_uncomp(const fe &x, const fe &y, uint32_t out[5]) {
   uint32_t w[16];

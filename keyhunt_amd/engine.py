@@ -19,9 +19,11 @@ HEADER = os.path.join(REPO, "include", "kh_gpu.h")
 
 KH_MODE_ADDRESS, KH_MODE_XPOINT, KH_MODE_ETH = 0, 1, 2
 KH_MODE_ENDO = 0x10  # OR into mode: -e
+KH_MODE_P2SH = 0x20  # OR into KH_MODE_ADDRESS: also probe the nested P2SH-P2WPKH digest of each 02/03 hash
 KH_SEARCH_COMPRESS, KH_SEARCH_UNCOMPRESS, KH_SEARCH_BOTH = 0, 1, 2
 KH_KIND_02, KH_KIND_03, KH_KIND_04, KH_KIND_XPOINT, KH_KIND_ETH = 0, 1, 2, 3, 5
 KH_KIND_ENDO1, KH_KIND_ENDO2, KH_KIND_NEGY = 0x10, 0x20, 0x40
+KH_KIND_P2SH = 0x80  # with KH_MODE_P2SH, OR'ed into KH_KIND_02/03: the nested digest matched
 TIME_ADDRESS, TIME_XPOINT, TIME_BSGS, TIME_BUILD, TIME_SETUP = 0, 1, 2, 3, 4
 KH_LAYER1_REFERENCE, KH_LAYER1_BLOCKED = 0, 1
 
@@ -136,6 +138,7 @@ def lib() -> ctypes.CDLL:
     L.kh_bloom_check.argtypes = [P, ctypes.c_uint32, u8p, ctypes.c_uint32, ctypes.c_uint32, u8p]
     L.kh_bloom_check2.argtypes = [P, ctypes.c_uint32, u8p, ctypes.c_uint32, ctypes.c_uint32, u8p, u8p]
     L.kh_digests.argtypes = [P, u8p, ctypes.c_uint32, u8p]
+    L.kh_digests_nested.argtypes = [P, u8p, ctypes.c_uint32, u8p]
     L.kh_filter_keys.argtypes = [P, u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]
     L.kh_tblk_check.argtypes = [P, u8p, ctypes.c_uint32, u8p]
     L.kh_scan_device_hits.argtypes = [P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
@@ -266,7 +269,8 @@ class Engine:
 
     def scan(self, start: int, n_keys: int, mode: int = KH_MODE_ADDRESS, search: int = KH_SEARCH_BOTH,
              stride: int = 1, cap: int = 4096, endo: bool = False) -> list[ScanHit]:
-        """endo: -e (also the endomorphism images; hit kinds then carry KH_KIND_ENDO1/2, KH_KIND_NEGY)."""
+        """endo: -e (also the endomorphism images; hit kinds then carry KH_KIND_ENDO1/2, KH_KIND_NEGY).
+        mode | KH_MODE_P2SH: also the nested P2SH-P2WPKH digests (hit kinds then carry KH_KIND_P2SH)."""
         hits = (KhHit * cap)()
         n = ctypes.c_uint32(0)
         r = lib().kh_scan(self._ctx, be32(start), be32(stride), n_keys, mode | (KH_MODE_ENDO if endo else 0), search,
@@ -535,6 +539,15 @@ class Engine:
         self._chk(lib().kh_digests(self._ctx, buf, len(points), out), "kh_digests")
         raw = out.raw
         return [tuple(raw[80 * i + 20 * k:80 * i + 20 * k + 20] for k in range(4)) for i in range(len(points))]
+
+    def digests_nested(self, points: list[tuple[int, int]]) -> list[tuple[bytes, bytes]]:
+        """Per (x, y): hash160(00 14 || hash160(02||X)) and hash160(00 14 || hash160(03||X)), the nested
+        P2SH-P2WPKH digests as the KH_MODE_P2SH walks compute them (kh_digests_nested)."""
+        buf = b"".join(be32(x) + be32(y) for x, y in points)
+        out = ctypes.create_string_buffer(40 * len(points))
+        self._chk(lib().kh_digests_nested(self._ctx, buf, len(points), out), "kh_digests_nested")
+        raw = out.raw
+        return [(raw[40 * i:40 * i + 20], raw[40 * i + 20:40 * i + 40]) for i in range(len(points))]
 
     def filter_keys(self, items: list[bytes], length: int) -> list[tuple[int, int]]:
         """Per 20-byte item the filter key pair (a, b) of its first `length` bytes (kh_filter_keys)."""

@@ -102,9 +102,9 @@ std::string b58enc(const uint8_t *d, int n) {
   for (auto it = buf.rbegin(); it != buf.rend(); ++it) s += B58[*it];
   return s;
 }
-std::string rmd_to_address(const uint8_t h[20]) {
+std::string rmd_to_address(const uint8_t h[20], uint8_t version = 0) {
   uint8_t d[25], c1[32], c2[32];
-  d[0] = 0;
+  d[0] = version;
   memcpy(d + 1, h, 20);
   sha256(d, 21, c1);
   sha256(c1, 32, c2);
@@ -164,7 +164,12 @@ struct options {
   bool have_minikey = false;
   std::string minikey_str;
   const char *alphabet = nullptr;
+  // --segwit (-m address; the reference has no such option): bc1q... lines are targets, a 3... line
+  // turns the nested P2SH-P2WPKH probes on (KH_MODE_P2SH), hits print their segwit forms
+  bool segwit = false;
 } opt;
+// --segwit: what the target reader saw -- bech32 P2WPKH rows, base58 lines of version byte 05
+uint64_t g_seg_bech32 = 0, g_seg_p2sh = 0;
 // keyhunt.cpp:419; ggsb and angrygiant walk like sequential (ggsb with BSGS_STEP = 2 x block size)
 const char *BSGS_MODES[7] = {"sequential", "backward", "both", "random", "dance", "ggsb", "angrygiant"};
 enum { BM_SEQUENTIAL, BM_BACKWARD, BM_BOTH, BM_RANDOM, BM_DANCE, BM_GGSB, BM_ANGRYGIANT };
@@ -179,7 +184,10 @@ U g_end;
 // ---------------------------------------------------------------------------------------------
 // hit output
 // ---------------------------------------------------------------------------------------------
-void writekey(kh_ctx *ctx, bool compressed, const uint8_t key[32]) {
+// nested (--segwit, a KH_KIND_P2SH hit): Address and rmd160 are the P2SH-P2WPKH ones, base58check of
+// 05 || hash160(00 14 || hash160(pubkey)).  Under --segwit a plain compressed hit gets a fifth line,
+// the key's bech32 P2WPKH address.
+void writekey(kh_ctx *ctx, bool compressed, const uint8_t key[32], bool nested = false) {
   // keyhunt.cpp:6891-6923
   uint8_t xy[64];
   kh_pubkeys(ctx, key, 1, xy);
@@ -199,17 +207,24 @@ void writekey(kh_ctx *ctx, bool compressed, const uint8_t key[32]) {
   }
   uint8_t rmd[20];
   memcpy(rmd, hw, 20);
-  std::string addr = rmd_to_address(rmd);
+  std::string fifth;
+  if (opt.segwit && compressed && !nested) fifth = "bech32 " + bech32_p2wpkh_encode(rmd) + "\n";
+  if (nested) {
+    uint32_t hn[5];
+    hash160_nested(hw, hn);
+    memcpy(rmd, hn, 20);
+  }
+  std::string addr = rmd_to_address(rmd, nested ? 5 : 0);
   std::string k = u_hex(u_from_be32(key));
   std::lock_guard<std::mutex> lk(g_keys_mtx);
   FILE *f = fopen("KEYFOUNDKEYFOUND.txt", "a+");
   if (f) {
-    fprintf(f, "Private Key: %s\npubkey: %s\nAddress %s\nrmd160 %s\n", k.c_str(), pub.c_str(), addr.c_str(),
-            hex(rmd, 20).c_str());
+    fprintf(f, "Private Key: %s\npubkey: %s\nAddress %s\nrmd160 %s\n%s", k.c_str(), pub.c_str(), addr.c_str(),
+            hex(rmd, 20).c_str(), fifth.c_str());
     fclose(f);
   }
-  printf("\nHit! Private Key: %s\npubkey: %s\nAddress %s\nrmd160 %s\n", k.c_str(), pub.c_str(), addr.c_str(),
-         hex(rmd, 20).c_str());
+  printf("\nHit! Private Key: %s\npubkey: %s\nAddress %s\nrmd160 %s\n%s", k.c_str(), pub.c_str(), addr.c_str(),
+         hex(rmd, 20).c_str(), fifth.c_str());
   fflush(stdout);
 }
 
@@ -366,6 +381,7 @@ std::vector<std::string> fgets_pieces(FILE *f, size_t cap) {
 //    the file lower the count.  (A blank line among them crashes the reference: strlen(NULL).)
 bool read_targets(const char *fn, int mode, std::vector<uint8_t> &rows, uint64_t &bloom_items,
                   std::vector<uint8_t> *adds = nullptr) {
+  g_seg_bech32 = g_seg_p2sh = 0;  // --segwit: the counts describe the file read by this call alone
   FILE *f = fopen(fn, "r");
   if (!f) {
     fprintf(stderr, "[E] Error opening the file %s\n", fn);
@@ -415,6 +431,13 @@ bool read_targets(const char *fn, int mode, std::vector<uint8_t> &rows, uint64_t
     const std::string ln = next < lines.size() ? lines[next++] : std::string();
     const size_t r = ln.size();
     bool ok = false;
+    if (opt.segwit && r == 42 && bech32_p2wpkh_decode(ln.c_str(), raw)) {
+      // --segwit: a mainnet P2WPKH address; its witness program is hash160(02/03||X), a plain row
+      rows.insert(rows.end(), raw, raw + 20);
+      if (adds) adds->insert(adds->end(), raw, raw + 20);
+      g_seg_bech32++;
+      ok = true;
+    }
     if (r > 0 && r <= 40) {
       if (r < 40 && is_base58(ln.c_str())) {
         size_t len = 25;
@@ -422,6 +445,7 @@ bool read_targets(const char *fn, int mode, std::vector<uint8_t> &rows, uint64_t
         if (len == 25) {
           rows.insert(rows.end(), raw + 1, raw + 21);
           if (adds) adds->insert(adds->end(), raw + 1, raw + 21);
+          if (opt.segwit && raw[0] == 5) g_seg_p2sh++;  // a 3... address: the run probes nested digests
           ok = true;
         }
       }
@@ -727,6 +751,8 @@ void addr_worker(addr_job *j) {
   uint8_t st_be[32], stride_be[32];
   u_to_be32(opt.stride, stride_be);
   const U span = u_mul_u64(opt.stride, j->nseq);
+  // --segwit with a 3... target in the file: every chunk also probes the nested digests
+  const uint32_t p2sh = opt.segwit && g_seg_p2sh ? KH_MODE_P2SH : 0;
   while (!r) {
     U base;
     {
@@ -753,11 +779,11 @@ void addr_worker(addr_job *j) {
     r = kh_scan(ctx, st_be, stride_be, j->nseq,
                 opt.mode == MODE_XPOINT ? (KH_MODE_XPOINT | (opt.endo ? KH_MODE_ENDO : 0))
                 : (opt.eth && (opt.mode == MODE_ADDRESS || opt.mode == MODE_RMD160)) ? (KH_MODE_ETH | (opt.endo ? KH_MODE_ENDO : 0))
-                      : (KH_MODE_ADDRESS | (opt.endo ? KH_MODE_ENDO : 0)),
+                      : (KH_MODE_ADDRESS | (opt.endo ? KH_MODE_ENDO : 0) | p2sh),
                 (uint32_t)opt.search, hits.data(), (uint32_t)hits.size(), &nh);
     if (r == KH_E_OVERFLOW && nh > hits.size()) {  // a short vanity prefix: take them all
       hits.resize(nh);
-      r = kh_scan(ctx, st_be, stride_be, j->nseq, KH_MODE_ADDRESS | (opt.endo ? KH_MODE_ENDO : 0),
+      r = kh_scan(ctx, st_be, stride_be, j->nseq, KH_MODE_ADDRESS | (opt.endo ? KH_MODE_ENDO : 0) | p2sh,
                   (uint32_t)opt.search, hits.data(), (uint32_t)hits.size(), &nh);
     }
     // KH_E_RANGE (--rmd-batch-size, a group centred on the key 0 mod n): the hits of the groups
@@ -772,7 +798,7 @@ void addr_worker(addr_job *j) {
       else if (opt.mode == MODE_VANITY)
         writevanitykey(ctx, hits[i].compressed != 0, hits[i].key);
       else
-        writekey(ctx, hits[i].compressed != 0, hits[i].key);
+        writekey(ctx, hits[i].compressed != 0, hits[i].key, (hits[i].kind & KH_KIND_P2SH) != 0);
     }
     if (r) {
       fprintf(stderr, "[E] kh_scan: %s (%s)\n", kh_strerror(r), kh_last_error(ctx));
@@ -1458,7 +1484,7 @@ void usage(const char *p) {
   printf("Usage: %s -m address|rmd160|xpoint|bsgs -f FILE [-b BITS | -r START:END] [-l compress|uncompress|both]\n"
          "       [-n N] [-k K] [-I STRIDE] [-g GPUS] [-q] [-s SECONDS] [-M] [-L blocked|reference]\n"
          "       [-e] [-c btc|eth] [-R] [-B sequential|backward|both|random|dance|angrygiant] [-S] [-6]\n"
-         "       [-z MULT] [-m vanity -v PREFIX ...] [--rmd-batch-size N] [-d] [-h]\n"
+         "       [-z MULT] [-m vanity -v PREFIX ...] [--rmd-batch-size N] [--segwit] [-d] [-h]\n"
 #ifdef KH_WITH_MINIKEYS
          "       -m minikeys -f FILE [-C MINIKEY] [-8 ALPHABET] [-n N] [-R]\n"
 #endif
@@ -1488,6 +1514,7 @@ int main(int argc, char **argv) {
                                            {"create-mapped", optional_argument, 0, 13},
                                            {"tmpdir", required_argument, 0, 14},
                                            {"rmd-batch-size", required_argument, 0, 15},
+                                           {"segwit", no_argument, 0, 16},
                                            {0, 0, 0, 0}};
   // --mapped-size / --bloom-bytes / --create-mapped N: the entry count and error the byte budget
   // allows (bloom_entries_for_bytes, keyhunt.cpp:7510-7530)
@@ -1607,6 +1634,7 @@ int main(int argc, char **argv) {
         opt.rmd_batch = (int)v;
         break;
       }
+      case 16: opt.segwit = true; break;  // -m address: bech32 and P2SH-P2WPKH targets (checked below)
       case 'm': {
         int m = -1;
         for (int i = 0; i < n_modes; i++)
@@ -1774,6 +1802,19 @@ int main(int argc, char **argv) {
     fprintf(stderr, "[E] Stride doesn't work with BSGS\n");
     return EXIT_FAILURE;
   }
+  // --segwit: -m address with compressed keys only, and no -S (the data_<hex>.dat cache keeps no address
+  // type, so a run that reads it could not know whether to probe the nested digests)
+  if (opt.segwit) {
+    const char *why = opt.mode != MODE_ADDRESS         ? "--segwit works with -m address only"
+                      : opt.eth                        ? "--segwit doesn't work with -c eth"
+                      : opt.search == KH_SEARCH_UNCOMPRESS ? "--segwit doesn't work with -l uncompress (segwit keys are compressed)"
+                      : opt.save_read                  ? "--segwit doesn't work with -S (the data file keeps no address type)"
+                                                       : nullptr;
+    if (why) {
+      fprintf(stderr, "[E] %s\n", why);
+      return EXIT_FAILURE;
+    }
+  }
   if (opt.stride_set) printf("[+] Stride : %s\n", u_dec(opt.stride).c_str());  // keyhunt.cpp:1195-1203
   if (opt.mode == MODE_BSGS) printf("[+] Mode BSGS %s\n", BSGS_MODES[opt.bsgs_mode]);  // keyhunt.cpp:1209-1211
   if (opt.mode == MODE_ADDRESS && !opt.crypto_given) printf("[+] Setting search for btc adddress\n");  // 1217-1220
@@ -1906,6 +1947,9 @@ int main(int argc, char **argv) {
     } else if (!read_targets(opt.file, opt.mode, rows, items, addp)) {
       return EXIT_FAILURE;
     }
+    if (opt.segwit)
+      printf("[+] Segwit targets: %llu bech32, %llu P2SH-P2WPKH\n", (unsigned long long)g_seg_bech32,
+             (unsigned long long)g_seg_p2sh);
     if (opt.mapped) {
       bool ok;
       if (opt.mode == MODE_VANITY) {  // the vanity bloom: the first min_bytes bytes of every A
@@ -1953,7 +1997,8 @@ int main(int argc, char **argv) {
       uint64_t need = 0;
       // (-m minikeys has no walk and no pad: a queue of a few MB per context)
       if (opt.mode != MODE_MINIKEYS &&
-          kh_scan_memory(nseq, smode | (opt.endo ? KH_MODE_ENDO : 0), (uint32_t)opt.search, &need) == KH_OK) {
+          kh_scan_memory(nseq, smode | (opt.endo ? KH_MODE_ENDO : 0) | (opt.segwit && g_seg_p2sh ? KH_MODE_P2SH : 0),
+                         (uint32_t)opt.search, &need) == KH_OK) {
         for (int dev = 0; dev < ndev && dev < gpus; dev++) {
           const uint64_t per = (uint64_t)(gpus / ndev + (dev < gpus % ndev ? 1 : 0));
           uint64_t fr = 0, tot = 0;

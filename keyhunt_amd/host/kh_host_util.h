@@ -353,6 +353,77 @@ inline bool is_base58(const char *s) {
   return true;
 }
 
+// BIP-173 bech32 for mainnet P2WPKH (--segwit): "bc1q" + the 20-byte witness program of version 0 as 32
+// five-bit groups + a 6-group checksum whose polymod constant is 1 (bech32m's, for version 1 and up, is
+// 0x2bc830a3 and is not accepted).  42 characters, all lower case or all upper case.
+inline const char *BECH32 = "qpzry9x8gf2tvdw0s3jn54khce6mua7l";
+inline uint32_t bech32_polymod(const uint8_t *v, size_t n) {
+  static const uint32_t GEN[5] = {0x3b6a57b2u, 0x26508e6du, 0x1ea119fau, 0x3d4233ddu, 0x2a1462b3u};
+  uint32_t chk = 1;
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t top = chk >> 25;
+    chk = ((chk & 0x1ffffffu) << 5) ^ v[i];
+    for (int j = 0; j < 5; j++)
+      if ((top >> j) & 1) chk ^= GEN[j];
+  }
+  return chk;
+}
+// the values the checksum runs over: hrp "bc" expanded {3, 3, 0, 2, 3}, then the data groups
+inline bool bech32_p2wpkh_decode(const char *s, uint8_t prog[20]) {
+  if (strlen(s) != 42) return false;
+  bool lower = false, upper = false;
+  uint8_t v[5 + 39] = {3, 3, 0, 2, 3};
+  char c[42];
+  for (int i = 0; i < 42; i++) {
+    lower |= s[i] >= 'a' && s[i] <= 'z';
+    upper |= s[i] >= 'A' && s[i] <= 'Z';
+    c[i] = (s[i] >= 'A' && s[i] <= 'Z') ? (char)(s[i] - 'A' + 'a') : s[i];
+  }
+  if (lower && upper) return false;
+  if (c[0] != 'b' || c[1] != 'c' || c[2] != '1') return false;
+  for (int i = 0; i < 39; i++) {
+    const char *p = c[3 + i] ? strchr(BECH32, c[3 + i]) : nullptr;
+    if (!p) return false;
+    v[5 + i] = (uint8_t)(p - BECH32);
+  }
+  if (bech32_polymod(v, sizeof v) != 1) return false;
+  if (v[5] != 0) return false;  // witness version 0
+  // 32 groups of 5 bits -> 20 bytes, no padding bits (160 = 32 * 5)
+  uint32_t acc = 0;
+  int bits = 0, o = 0;
+  for (int i = 0; i < 32; i++) {
+    acc = (acc << 5) | v[6 + i];
+    bits += 5;
+    if (bits >= 8) {
+      bits -= 8;
+      prog[o++] = (uint8_t)(acc >> bits);
+      acc &= (1u << bits) - 1u;
+    }
+  }
+  return o == 20 && bits == 0;
+}
+inline std::string bech32_p2wpkh_encode(const uint8_t prog[20]) {
+  uint8_t v[5 + 39] = {3, 3, 0, 2, 3};
+  v[5] = 0;
+  uint32_t acc = 0;
+  int bits = 0, o = 6;
+  for (int i = 0; i < 20; i++) {
+    acc = (acc << 8) | prog[i];
+    bits += 8;
+    while (bits >= 5) {
+      bits -= 5;
+      v[o++] = (uint8_t)((acc >> bits) & 31u);
+    }
+    acc &= (1u << bits) - 1u;
+  }
+  for (int i = 0; i < 6; i++) v[38 + i] = 0;
+  const uint32_t pm = bech32_polymod(v, sizeof v) ^ 1u;
+  for (int i = 0; i < 6; i++) v[38 + i] = (uint8_t)((pm >> (5 * (5 - i))) & 31u);
+  std::string s = "bc1";
+  for (int i = 0; i < 39; i++) s += BECH32[v[5 + i]];
+  return s;
+}
+
 // addvanity (keyhunt.cpp:6739-6866): the hash160 ranges [A_j, B_j] of the addresses that start
 // with `target` (padded with '1' for A, 'z' for B up to each 25-byte decoding length), appended to
 // `ranges` (40 bytes each); min_bytes tracks the common-prefix length the vanity bloom keys on.
