@@ -277,19 +277,19 @@ void sha256_bytes(const uint8_t *p, size_t n, uint8_t out[32]) {
 
 // The blocked target filter the walk probes for exact targets (kh_kernels.hip tblk_probe): 16-byte
 // blocks, KH_BLK_BITS_MUL x the reference bloom's bits; row words w = little-endian u32s of the
-// 20 bytes: block (w0 * blocks) >> 32, bits from w1, w2 (, w3) as kh_blk_masks (kh_kernels.h).
+// 20 bytes: block (w0 * blocks) >> 32, bits from w1, w2 as kh_blk_masks (kh_kernels.h).
 int upload_tblk(kh_ctx *c) {
   const uint64_t blocks = (c->tbd.bits * KH_BLK_BITS_MUL + 127) / 128;
   std::vector<uint4> words(blocks, make_uint4(0, 0, 0, 0));
   for (uint64_t r = 0; r < c->n_rows; r++) {
     const uint8_t *p = &c->rows[r * 20];
-    uint32_t w[4];
-    for (int k = 0; k < 4; k++)
+    uint32_t w[3];
+    for (int k = 0; k < 3; k++)
       w[k] = (uint32_t)p[4 * k] | ((uint32_t)p[4 * k + 1] << 8) | ((uint32_t)p[4 * k + 2] << 16) |
              ((uint32_t)p[4 * k + 3] << 24);
     const uint64_t blk = ((uint64_t)w[0] * blocks) >> 32;
     uint32_t m[4];
-    kh_blk_masks(w[1], w[2], w[3], m);
+    kh_blk_masks(w[1], w[2], m);
     words[blk].x |= m[0];
     words[blk].y |= m[1];
     words[blk].z |= m[2];

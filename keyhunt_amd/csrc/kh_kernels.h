@@ -42,10 +42,6 @@ static_assert(KH_WALK_H >= 64 && KH_WALK_H <= 512 && (512 % KH_WALK_H) == 0,
 #ifndef KH_WALK_LB
 #define KH_WALK_LB 4
 #endif
-// compute hash160(02||X) and hash160(03||X) with interleaved SHA-256 chains
-#ifndef KH_HASH_PAIR
-#define KH_HASH_PAIR 1
-#endif
 // KH_WALK_LB_H160CB: the compressed exact-target hash walk (the bench's rmd160 leg) at 4 waves/SIMD.  Since
 // the hash IVs fold (round 5) it fits 128 VGPRs with no spill in its per-point loop: +0.3 % in an
 // interleaved A/B, spreads disjoint (profiles/r05g_ab_hash_4waves.json); round 4 measured -1.1 % with the
@@ -75,17 +71,12 @@ static_assert(KH_WALK_H >= 64 && KH_WALK_H <= 512 && (512 % KH_WALK_H) == 0,
 
 // Bit positions of the split-block filters (blocked layer 1 above, and the exact-target filter of
 // kh_kernels.hip tblk_probe), from an item's position words s0, s1 (layer 1: the big-endian u32s of
-// X[12..16), X[16..20); targets: w1, w2).  KH_PK_MASKS (default): block word w (< 4) gets 4 bits, 2 in
-// each 16-bit half: with s = s_{w/2}, a = s >> 8*(w%2) and b = a >> 4, the bits
+// X[12..16), X[16..20); targets: w1, w2).  Block word w (< 4) gets 4 bits, 2 in each 16-bit half: with
+// s = s_{w/2}, a = s >> 8*(w%2) and b = a >> 4, the bits
 //   a & 15,  16 + ((a >> 16) & 15),  b & 15,  16 + ((b >> 16) & 15)
 // -- each pair is one v_pk_lshlrev_b16 of 0x00010001, so the 16 positions cost 6 shifts and 8 packed
-// shifts (the 5-bit-field form below, KH_PK_MASKS=0, costs two 32-bit shifts per position).  Every
-// bit of s0 and s1 is used once; per 16-bit half the FP model is the same as per 32-bit word.
-// KH_PK_MASKS=0: fields f < 16 of X[12..24) (s0, s1, s2 = X[20..24)), (s_{f/6} >> 5*(f%6)) & 31, bits
-// 4w..4w+3 in word w.
-#ifndef KH_PK_MASKS
-#define KH_PK_MASKS 1
-#endif
+// shifts.  Every bit of s0 and s1 is used once; per 16-bit half the FP model is the same as per 32-bit
+// word.
 // (1 << (a & 15)) | (1 << (16 + ((a >> 16) & 15)))
 KH_HD uint32_t kh_pk_bits(uint32_t a) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -96,88 +87,12 @@ KH_HD uint32_t kh_pk_bits(uint32_t a) {
   return (1u << (a & 15u)) | (1u << (16u + ((a >> 16) & 15u)));
 #endif
 }
-KH_HD void kh_blk_masks(uint32_t s0, uint32_t s1, uint32_t s2, uint32_t m[4]) {
-  if (KH_PK_MASKS) {
-    (void)s2;
-    m[0] = kh_pk_bits(s0) | kh_pk_bits(s0 >> 4);
-    m[1] = kh_pk_bits(s0 >> 8) | kh_pk_bits(s0 >> 12);
-    m[2] = kh_pk_bits(s1) | kh_pk_bits(s1 >> 4);
-    m[3] = kh_pk_bits(s1 >> 8) | kh_pk_bits(s1 >> 12);
-    return;
-  }
-  uint32_t f[16];
-  for (int t = 0; t < 16; t++) {
-    const uint32_t s = t < 6 ? s0 : t < 12 ? s1 : s2;
-    f[t] = 1u << ((s >> (5 * (t % 6))) & 31u);
-  }
-  for (int w = 0; w < 4; w++) m[w] = f[4 * w] | f[4 * w + 1] | f[4 * w + 2] | f[4 * w + 3];
+KH_HD void kh_blk_masks(uint32_t s0, uint32_t s1, uint32_t m[4]) {
+  m[0] = kh_pk_bits(s0) | kh_pk_bits(s0 >> 4);
+  m[1] = kh_pk_bits(s0 >> 8) | kh_pk_bits(s0 >> 12);
+  m[2] = kh_pk_bits(s1) | kh_pk_bits(s1 >> 4);
+  m[3] = kh_pk_bits(s1 >> 8) | kh_pk_bits(s1 >> 12);
 }
-
-// Variant switches of the BSGS giant walk (k_walk<KM_BSGSB, KH_WALK_HB>), A/B-measured:
-//   KH_TAB_LDS   the delta table staged in LDS (one 1024-thread workgroup per CU, ds_read_b128
-//                broadcasts) instead of scalar-cache reads into SGPRs
-//   KH_TAB_VCOPY the table values a step uses twice copied to VGPRs once (a carry chain with an SGPR
-//                operand and a carry-in reads two scalars, over gfx9's constant-bus limit of one, so
-//                the compiler copies the SGPR in every such instruction)
-//   KH_SPARSE_ALL the half-size inversion pad (even prefix products only) in every mode, not only BSGS
-//   KH_SPARSE_BSGS the half-size pad in the BSGS walks (default on)
-#ifndef KH_TAB_LDS
-#define KH_TAB_LDS 0
-#endif
-#ifndef KH_TAB_VCOPY
-#define KH_TAB_VCOPY 0
-#endif
-#ifndef KH_SPARSE_BSGS
-#define KH_SPARSE_BSGS 1
-#endif
-//   KH_SPARSE_XPOINT the sparse pad (even prefix products only) for -m xpoint's blocked walk too
-//                  (round 4, with KH_SPARSE_KEEP: +1.5 %, profiles/r04o_sparse_xpoint_ab.json)
-#ifndef KH_SPARSE_XPOINT
-#define KH_SPARSE_XPOINT 1
-#endif
-#ifndef KH_SPARSE_ALL
-#define KH_SPARSE_ALL 0
-#endif
-//   KH_SPARSE_KEEP the sparse pad's backward pass keeps the loaded even row as loaded for the two
-//                  steps it serves (one read per row; the load lands in place and flies for a step)
-#ifndef KH_SPARSE_KEEP
-#define KH_SPARSE_KEEP 1
-#endif
-//   KH_PAD_PLANES  the two 16-B halves of every inversion-pad entry in separate planes (kh_kernels.hip
-//                  pad_idx): one wave access covers 1 KB contiguously instead of 2 KB with holes
-#ifndef KH_PAD_PLANES
-#define KH_PAD_PLANES 0
-#endif
-//   KH_PAD_NT      the inversion pad's stores (bit 0) / loads (bit 1) with the nontemporal hint
-#ifndef KH_PAD_NT
-#define KH_PAD_NT 0
-#endif
-//   KH_PROBE_EARLY the deferred walks issue the previous pair's block loads at the top of a step,
-//                  before its inverse, instead of after it
-#ifndef KH_PROBE_EARLY
-#define KH_PROBE_EARLY 0
-#endif
-//   KH_XPOINT_DEFER -m xpoint against the blocked target filter walks like the BSGS giant walk: a
-//                pair's two 16-B filter loads are issued one step later and tested after that
-//                step's field math (k_walk<KM_XPOINTB>), and -(dy) = T.y + C.y replaces the negation
-#ifndef KH_XPOINT_DEFER
-#define KH_XPOINT_DEFER 1
-#endif
-//   KH_FULL_GROUPS the xpoint deferred-probe walk skips the per-pair index-vs-job-end compares in
-//                groups that lie wholly inside the job for every lane of the wave (a uniform test)
-#ifndef KH_FULL_GROUPS
-#define KH_FULL_GROUPS 1
-#endif
-//   KH_H160_BLK  -l compress hash160 scans with exact targets compile the blocked-filter probe alone
-//                (k_walk<KM_H160CB>), so the RIPEMD-160 steps that feed digest words 3..4 drop out
-#ifndef KH_H160_BLK
-#define KH_H160_BLK 1
-#endif
-//   KH_NESTED_PAIR the KM_P2SH walks nest a point's 02 and 03 digests together (hash160_nested2: the two
-//                SHA-256 blocks interleaved) instead of one after the other in the rolled prefix loop
-#ifndef KH_NESTED_PAIR
-#define KH_NESTED_PAIR 1
-#endif
 
 enum kh_walk_mode {
   KM_H160C = 0,   // hash160(02||X), hash160(03||X)          -l compress
@@ -331,14 +246,14 @@ namespace kh {
 hipError_t launch_mini_filter(const mini_filter_args &A, hipStream_t st);
 hipError_t launch_mini_keys(const mini_keys_args &A, hipStream_t st);
 hipError_t launch_walk(int mode, const walk_args &A, hipStream_t st, int H = KH_WALK_H);
-// Inversion-pad rows per lane the walk launch_walk runs for (mode, blocked target filter) touches: the
-// sparse-pad walks (k_walk's SPARSE: the BSGS giant walks, -m xpoint against the blocked filter) keep
-// only the even prefix products, rows [0, H/2); the others all H
+// The sparse-pad walks -- the BSGS giant walks and -m xpoint against the blocked target filter -- keep
+// only the even prefix products in the inversion pad (kh_kernels.hip k_walk)
+constexpr bool walk_sparse(int mode) { return mode == KM_BSGSB || mode == KM_BSGS || mode == KM_XPOINTB; }
+// Inversion-pad rows per lane the walk launch_walk runs for (mode, blocked target filter) touches:
+// rows [0, H/2) for a sparse-pad walk, all H otherwise
 inline int walk_pad_rows(int mode, bool tblk, int H) {
-  if (KH_XPOINT_DEFER && mode == KM_XPOINT && tblk) mode = KM_XPOINTB;
-  const bool sparse = KH_SPARSE_ALL || (KH_SPARSE_BSGS && (mode == KM_BSGSB || mode == KM_BSGS)) ||
-                      (KH_SPARSE_XPOINT && mode == KM_XPOINTB);
-  return sparse ? H / 2 : H;
+  if (mode == KM_XPOINT && tblk) mode = KM_XPOINTB;
+  return walk_sparse(mode) ? H / 2 : H;
 }
 hipError_t launch_walk_zinv(int mode, const walk_args &A, hipStream_t st);
 hipError_t launch_refine(const refine_args &A, hipStream_t st);

@@ -56,23 +56,16 @@ __device__ __forceinline__ void store_soa(uint32_t *__restrict__ base, uint32_t 
 #pragma unroll
   for (int i = 0; i < 8; i++) base[(size_t)i * L + g] = r.d[i];
 }
-// Pad entry `slot` = row * L + g (lane g) as two 16-B halves.  KH_PAD_PLANES: the halves of a row
-// live in two planes of L entries each, so one 16-B access of a wave covers 1 KB contiguously
-// (16 lines) instead of 2 KB with 16-B holes (32 lines, each touched again by the other half)
+// Pad entry `slot` = row * L + g (lane g) as two 16-B halves, side by side.  g and L are not read; they
+// stay in the pad helpers' signatures because k_walk's backward step captures them at its first pad
+// access, and without that the walks allocate a few registers differently.
 __device__ __forceinline__ size_t pad_idx(size_t slot, uint32_t g, size_t L, int h) {
-  if constexpr (KH_PAD_PLANES) return 2 * slot - g + (h ? L : 0);
   (void)g;
   (void)L;
   return 2 * slot + h;
 }
 typedef uint32_t pad4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void scr_store(uint4 *__restrict__ scr, size_t slot, const fe &a, uint32_t g, size_t L) {
-  if constexpr (KH_PAD_NT & 1) {
-    pad4 *p = reinterpret_cast<pad4 *>(scr);
-    __builtin_nontemporal_store(pad4{a.d[0], a.d[1], a.d[2], a.d[3]}, p + pad_idx(slot, g, L, 0));
-    __builtin_nontemporal_store(pad4{a.d[4], a.d[5], a.d[6], a.d[7]}, p + pad_idx(slot, g, L, 1));
-    return;
-  }
   scr[pad_idx(slot, g, L, 0)] = make_uint4(a.d[0], a.d[1], a.d[2], a.d[3]);
   scr[pad_idx(slot, g, L, 1)] = make_uint4(a.d[4], a.d[5], a.d[6], a.d[7]);
 }
@@ -80,13 +73,8 @@ __device__ __forceinline__ void scr_store(uint4 *__restrict__ scr, size_t slot, 
 __device__ __forceinline__ void scr_load_raw(pad4 &u, pad4 &v, const uint4 *__restrict__ scr, size_t slot, uint32_t g,
                                              size_t L) {
   const pad4 *p = reinterpret_cast<const pad4 *>(scr);
-  if constexpr (KH_PAD_NT & 2) {
-    u = __builtin_nontemporal_load(p + pad_idx(slot, g, L, 0));
-    v = __builtin_nontemporal_load(p + pad_idx(slot, g, L, 1));
-  } else {
-    u = p[pad_idx(slot, g, L, 0)];
-    v = p[pad_idx(slot, g, L, 1)];
-  }
+  u = p[pad_idx(slot, g, L, 0)];
+  v = p[pad_idx(slot, g, L, 1)];
 }
 __device__ __forceinline__ void pad_unpack(fe &a, const pad4 &u, const pad4 &v) {
   a.d[0] = u.x; a.d[1] = u.y; a.d[2] = u.z; a.d[3] = u.w;
@@ -146,25 +134,21 @@ __device__ __forceinline__ void bloom_insert(uint8_t *__restrict__ bf_base, uint
 __device__ __forceinline__ uint32_t blk_index(uint32_t w5, const bloom_desc &bd) {
   return (uint32_t)(((uint64_t)w5 * bd.bits) >> 32);
 }
-// masks of the four block words from s0 = limb 4, s1 = limb 3, s2 = limb 2 (kh_kernels.h
-// kh_blk_masks: packed 16-bit shifts, or `1u << (s >> k)` per 5-bit field with KH_PK_MASKS=0)
-__device__ __forceinline__ void blk_masks(uint32_t s0, uint32_t s1, uint32_t s2, uint32_t m[4]) {
-  kh_blk_masks(s0, s1, s2, m);
-}
-__device__ __forceinline__ bool blk_match(const uint4 &v, uint32_t s0, uint32_t s1, uint32_t s2) {
+// the block v covers the masks of position words s0, s1 (kh_kernels.h kh_blk_masks; layer 1: limbs 4, 3)
+__device__ __forceinline__ bool blk_match(const uint4 &v, uint32_t s0, uint32_t s1) {
   uint32_t m[4];
 #ifdef KH_TIMING_CHEAP_MASKS
   // timing-only build: the probe without mask arithmetic (hits are wrong); prices the masks
-  m[0] = s0 | 0x80000001u; m[1] = s1 | 0x80000001u; m[2] = s2 | 0x80000001u; m[3] = (s0 ^ s1) | 0x80000001u;
+  m[0] = s0 | 0x80000001u; m[1] = s1 | 0x80000001u; m[2] = (s0 & s1) | 0x80000001u; m[3] = (s0 ^ s1) | 0x80000001u;
 #else
-  blk_masks(s0, s1, s2, m);
+  kh_blk_masks(s0, s1, m);
 #endif
   // a miss is a mask bit its block word lacks: OR the four words' misses and compare once
   return ((m[0] & ~v.x) | (m[1] & ~v.y) | (m[2] & ~v.z) | (m[3] & ~v.w)) == 0;
 }
 __device__ __forceinline__ void blk_insert(uint8_t *__restrict__ bf_shard, const bloom_desc &bd, const fe &x) {
   uint32_t m[4];
-  blk_masks(x.d[4], x.d[3], x.d[2], m);
+  kh_blk_masks(x.d[4], x.d[3], m);
   uint32_t *w = reinterpret_cast<uint32_t *>(bf_shard + (size_t)blk_index(x.d[5], bd) * 16);
 #pragma unroll
   for (int k = 0; k < 4; k++) atomicOr(&w[k], m[k]);
@@ -194,7 +178,7 @@ __device__ __forceinline__ void x_bytes_u64(const fe &x, uint64_t in[4]) {
 // host's exact table search (searchbinary), so the reported hits are the reference's.
 __device__ __forceinline__ bool tblk_probe_at(const uint4 *tblk, uint32_t tblocks, const uint32_t w[5]) {
   const uint32_t blk = (uint32_t)(((uint64_t)w[0] * tblocks) >> 32);
-  return blk_match(tblk[blk], w[1], w[2], w[3]);
+  return blk_match(tblk[blk], w[1], w[2]);
 }
 __device__ __forceinline__ bool tblk_probe(const walk_args &A, const uint32_t w[5]) {
   return tblk_probe_at(A.tblk, A.tblocks, w);
@@ -212,32 +196,25 @@ __device__ __forceinline__ bool probe_h160(const walk_args &A, const uint32_t h[
   return bloom_probe_lazy(A.bloom, A.bd, a, [&](uint64_t s) { return xxh64_prefix(h, A.probe_len, s); });
 }
 
-// KM_P2SH: the nested digests hash160(00 14 || h) of a point's two plain digests against the filter
-// the plain ones were probed in; kinds 0/1 | KH_DKIND_P2SH | tag.  BLK: the blocked target filter only
-// (the filter reads words 0..2, so the nested RIPEMD-160's steps that feed only words 3..4 are dead)
+// KM_P2SH: the nested digests hash160(00 14 || h) of a point's two plain digests (hash160_nested2: the two
+// SHA-256 blocks interleaved) against the filter the plain ones were probed in; kinds 0/1 | KH_DKIND_P2SH | tag.
+// BLK: the blocked target filter only (the filter reads words 0..2, so the nested RIPEMD-160's steps that feed
+// only words 3..4 are dead)
 template <bool BLK>
 __device__ __forceinline__ void probe_nested(const walk_args &A, const uint32_t hh[2][5], uint64_t idx, uint32_t tag) {
-#if KH_NESTED_PAIR
   uint32_t nn[2][5];
   hash160_nested2(hh[0], hh[1], nn[0], nn[1]);
-#endif
 #pragma unroll 1
   for (uint32_t k = 0; k < 2; k++) {
     uint32_t n[5];
-#if KH_NESTED_PAIR
 #pragma unroll
     for (int q = 0; q < 5; q++) n[q] = k ? nn[1][q] : nn[0][q];
-#else
-    uint32_t h[5];
-#pragma unroll
-    for (int q = 0; q < 5; q++) h[q] = k ? hh[1][q] : hh[0][q];
-    hash160_nested(h, n);
-#endif
     if (BLK ? tblk_probe(A, n) : probe_h160(A, n)) record_hit(A, idx, k | KH_DKIND_P2SH | tag);
   }
 }
 
-// hash160(02||X) and hash160(03||X) of one x-coordinate into the target bloom; kinds 0/1 | tag
+// hash160(02||X) and hash160(03||X) of one x-coordinate (interleaved SHA-256 chains) into the target
+// filter; kinds 0/1 | tag
 template <bool P2SH = false>
 __device__ __forceinline__ void probe_comp(const walk_args &A, const fe &x, uint64_t idx, uint32_t tag) {
   if constexpr (P2SH) {
@@ -255,7 +232,6 @@ __device__ __forceinline__ void probe_comp(const walk_args &A, const fe &x, uint
     probe_nested<false>(A, hh, idx, tag);
     return;
   }
-#if KH_HASH_PAIR
   uint32_t hh[2][5];
   hash160_comp2(x, hh[0], hh[1]);
 #pragma unroll 1
@@ -265,14 +241,6 @@ __device__ __forceinline__ void probe_comp(const walk_args &A, const fe &x, uint
     for (int q = 0; q < 5; q++) h[q] = k ? hh[1][q] : hh[0][q];
     if (probe_h160(A, h)) record_hit(A, idx, k | tag);
   }
-#else
-#pragma unroll 1
-  for (uint32_t pfx = 2; pfx <= 3; pfx++) {
-    uint32_t h[5];
-    hash160_comp(x, pfx, h);
-    if (probe_h160(A, h)) record_hit(A, idx, (pfx - 2) | tag);
-  }
-#endif
 }
 // hash160(04||X||Y); kind 2 | tag
 __device__ __forceinline__ void probe_uncomp(const walk_args &A, const fe &x, const fe &y, uint64_t idx, uint32_t tag) {
@@ -280,17 +248,22 @@ __device__ __forceinline__ void probe_uncomp(const walk_args &A, const fe &x, co
   hash160_uncomp(x, y, h);
   if (probe_h160(A, h)) record_hit(A, idx, 2 | tag);
 }
+// a 20-byte exact item w (X[0..20), an eth address): the blocked target filter if the job has one, else
+// the target bloom with its second hash computed lazily; a hit is recorded with `kind`
+__device__ __forceinline__ void probe_exact20(const walk_args &A, const uint32_t w[5], uint64_t idx, uint32_t kind) {
+  if (A.tblk) {
+    if (tblk_probe(A, w)) record_hit(A, idx, kind);
+    return;
+  }
+  uint64_t a = xxh64_20(w, KH_BLOOM_SEED);
+  if (bloom_probe_lazy(A.bloom, A.bd, a, [&](uint64_t s) { return xxh64_20(w, s); })) record_hit(A, idx, kind);
+}
 // X[0..20); kind 3 | tag
 __device__ __forceinline__ void probe_xpoint(const walk_args &A, const fe &x, uint64_t idx, uint32_t tag) {
   uint32_t w[5];
 #pragma unroll
   for (int j = 0; j < 5; j++) w[j] = bswap32(x.d[7 - j]);
-  if (A.tblk) {
-    if (tblk_probe(A, w)) record_hit(A, idx, 3 | tag);
-    return;
-  }
-  uint64_t a = xxh64_20(w, KH_BLOOM_SEED);
-  if (bloom_probe_lazy(A.bloom, A.bd, a, [&](uint64_t s) { return xxh64_20(w, s); })) record_hit(A, idx, 3 | tag);
+  probe_exact20(A, w, idx, 3 | tag);
 }
 // beta and beta^2 (cube roots of unity mod p): lambda*(x, y) = (beta*x, y) (-e, keyhunt.cpp:926-930)
 __device__ __forceinline__ void endo_beta(fe &b, int e) {
@@ -307,12 +280,7 @@ __device__ __forceinline__ void probe_eth(const walk_args &A, const fe &x, const
                                           uint32_t tag = 0) {
   uint32_t w[5];
   eth_address(x, y, w);
-  if (A.tblk) {
-    if (tblk_probe(A, w)) record_hit(A, idx, 5 | tag);
-    return;
-  }
-  uint64_t a = xxh64_20(w, KH_BLOOM_SEED);
-  if (bloom_probe_lazy(A.bloom, A.bd, a, [&](uint64_t s) { return xxh64_20(w, s); })) record_hit(A, idx, 5 | tag);
+  probe_exact20(A, w, idx, 5 | tag);
 }
 
 template <int MODE>
@@ -452,14 +420,11 @@ __device__ __forceinline__ uint4 ld_nt16(const uint4 *p) {
   v4u32 v = __builtin_nontemporal_load(reinterpret_cast<const v4u32 *>(p));
   return make_uint4(v.x, v.y, v.z, v.w);
 }
-// {block index within the shard, limbs 4, 3, and the shard byte in the top 8 bits of the last word}
-// of one point (KH_PK_MASKS=0: limb 2, whose bits 0..19 are all its masks read).  The record
-// addresses any layer whose shards are < 4 GB (the whole layer < 1 TB; a global 16-B block index in
-// 32 bits would stop at 64 GB).
+// {block index within the shard, limbs 4, 3 (the masks' position words), limb 7 (its top 8 bits are
+// the shard byte)} of one point.  The record addresses any layer whose shards are < 4 GB (the whole
+// layer < 1 TB; a global 16-B block index in 32 bits would stop at 64 GB).
 __device__ __forceinline__ uint4 blk_record(const walk_args &A, const fe &x) {
-  // the packed-shift masks read limbs 4 and 3 only: the shard byte rides as limb 7 itself
-  if constexpr (KH_PK_MASKS) return make_uint4(blk_index(x.d[5], A.bd), x.d[4], x.d[3], x.d[7]);
-  return make_uint4(blk_index(x.d[5], A.bd), x.d[4], x.d[3], (x.d[2] & 0x000FFFFFu) | (x.d[7] & 0xFF000000u));
+  return make_uint4(blk_index(x.d[5], A.bd), x.d[4], x.d[3], x.d[7]);
 }
 __device__ __forceinline__ uint4 blk_load(const walk_args &A, const uint4 &r) {
 #ifdef KH_TIMING_NO_PROBE_LOADS
@@ -469,20 +434,16 @@ __device__ __forceinline__ uint4 blk_load(const walk_args &A, const uint4 &r) {
   // timing-only build: every probe reads a block of the layer's first 2^LOG2 blocks, a region
   // that stays on die (Infinity Cache / L2) -- the loads without their HBM traffic (outputs wrong)
   return ld_nt16(reinterpret_cast<const uint4 *>(A.bloom) + (r.x & ((1u << KH_TIMING_PROBE_REGION_LOG2) - 1u)));
-#elif defined(KH_PROBE_PLAIN_LOAD)
-  const uint8_t *shard = A.bloom + (uint64_t)(r.w >> 24) * A.bstride32;
-  return reinterpret_cast<const uint4 *>(shard)[r.x];
 #else
   const uint8_t *shard = A.bloom + (uint64_t)(r.w >> 24) * A.bstride32;
   return ld_nt16(reinterpret_cast<const uint4 *>(shard) + r.x);
 #endif
 }
-__device__ __forceinline__ bool blk_match_rec(const uint4 &v, const uint4 &r) { return blk_match(v, r.y, r.z, r.w); }
-// {target-filter block, w1, w2, w3} of X[0..20), w_j = bswap32(limb 7 - j) as in probe_xpoint /
+__device__ __forceinline__ bool blk_match_rec(const uint4 &v, const uint4 &r) { return blk_match(v, r.y, r.z); }
+// {target-filter block, w1, w2, 0} of X[0..20), w_j = bswap32(limb 7 - j) as in probe_xpoint /
 // tblk_probe: the -m xpoint probe record that crosses the loop edge in k_walk<KM_XPOINTB>
 __device__ __forceinline__ uint4 tblk_record(const walk_args &A, const fe &x) {
-  return make_uint4((uint32_t)(((uint64_t)bswap32(x.d[7]) * A.tblocks) >> 32), bswap32(x.d[6]), bswap32(x.d[5]),
-                    KH_PK_MASKS ? 0u : bswap32(x.d[4]));  // w3 feeds only the 5-bit-field masks
+  return make_uint4((uint32_t)(((uint64_t)bswap32(x.d[7]) * A.tblocks) >> 32), bswap32(x.d[6]), bswap32(x.d[5]), 0u);
 }
 // one blocked probe, in place (the group centre)
 __device__ __forceinline__ void blk_probe(const walk_args &A, const fe &x, uint64_t idx) {
@@ -559,61 +520,13 @@ constexpr int walk_lb() {
                                                                     : KH_WALK_LB;
 }
 
-// KH_TAB_LDS: the giant walk's table in LDS, one 1024-thread workgroup per CU
-template <int MODE, int H>
-constexpr bool tab_lds() {
-  return KH_TAB_LDS && MODE == KM_BSGSB && H == KH_WALK_HB;
-}
-template <int MODE, int H>
-constexpr int walk_threads() {
-  return tab_lds<MODE, H>() ? 1024 : 256;
-}
-template <int MODE, int H>
-constexpr int walk_blocks_per_cu() {
-  return tab_lds<MODE, H>() ? 1 : walk_lb<MODE>();  // either way walk_lb waves per SIMD
-}
-// a uniform 32-bit value copied into a VGPR (KH_TAB_VCOPY): later carry chains then read it there
-__device__ __forceinline__ uint32_t to_vgpr(uint32_t s) {
-  uint32_t v;
-  asm("v_mov_b32 %0, %1" : "=v"(v) : "s"(s));
-  return v;
-}
-__device__ __forceinline__ void fe_to_vgpr(fe &a) {
-#pragma unroll
-  for (int i = 0; i < 8; i++) a.d[i] = to_vgpr(a.d[i]);
-}
-
 template <int MODE, int H = KH_WALK_H>
-__global__ void __launch_bounds__((walk_threads<MODE, H>()), (walk_blocks_per_cu<MODE, H>())) k_walk(walk_args A) {
+__global__ void __launch_bounds__(256, (walk_lb<MODE>())) k_walk(walk_args A) {
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  constexpr bool LDS = tab_lds<MODE, H>();
-  // table entry i: x in words [0,8), y in [8,16); LDS: uint4 [i*4 .. i*4+3]
-  __shared__ uint4 tabl[LDS ? (H + 1) * 4 : 1];
-  if constexpr (LDS) {
-    const uint4 *src = reinterpret_cast<const uint4 *>(A.tab);
-    for (uint32_t k = threadIdx.x; k < (uint32_t)(H + 1) * 4; k += blockDim.x) tabl[k] = src[k];
-    __syncthreads();
-  }
   if (g >= A.L) return;
-  kconst_ptr T = (kconst_ptr)A.tab;  // (H+1) x {x[8], y[8]}, wave-uniform reads
-  auto ld_tx = [&](fe &x, int i) {
-    if constexpr (LDS) {
-      const uint4 a = tabl[i * 4], b = tabl[i * 4 + 1];
-      x.d[0] = a.x; x.d[1] = a.y; x.d[2] = a.z; x.d[3] = a.w;
-      x.d[4] = b.x; x.d[5] = b.y; x.d[6] = b.z; x.d[7] = b.w;
-    } else {
-      load_fe_k(x, T + i * 16);
-    }
-  };
-  auto ld_ty = [&](fe &y, int i) {
-    if constexpr (LDS) {
-      const uint4 a = tabl[i * 4 + 2], b = tabl[i * 4 + 3];
-      y.d[0] = a.x; y.d[1] = a.y; y.d[2] = a.z; y.d[3] = a.w;
-      y.d[4] = b.x; y.d[5] = b.y; y.d[6] = b.z; y.d[7] = b.w;
-    } else {
-      load_fe_k(y, T + i * 16 + 8);
-    }
-  };
+  kconst_ptr T = (kconst_ptr)A.tab;  // (H+1) x {x[8], y[8]}: x in words [0,8), y in [8,16); wave-uniform reads
+  auto ld_tx = [&](fe &x, int i) { load_fe_k(x, T + i * 16); };
+  auto ld_ty = [&](fe &y, int i) { load_fe_k(y, T + i * 16 + 8); };
   uint4 *__restrict__ scr = A.scratch;
   const size_t L = A.L;
   fe cx, cy;
@@ -622,8 +535,7 @@ __global__ void __launch_bounds__((walk_threads<MODE, H>()), (walk_blocks_per_cu
 
   // BSGS and xpoint walks keep only the even prefix products in the pad and rebuild each odd one
   // with one multiplication in the backward pass: half the pad traffic for +1/2 multiplication per pair
-  constexpr bool SPARSE = KH_SPARSE_ALL || (KH_SPARSE_BSGS && (MODE == KM_BSGSB || MODE == KM_BSGS)) ||
-                          (KH_SPARSE_XPOINT && MODE == KM_XPOINTB);
+  constexpr bool SPARSE = walk_sparse(MODE);
 #ifdef KH_TIMING_PAD_ROWS_LOG2
   // timing-only build: the pad's stores (KH_TIMING_PAD_FOLD & 1) and/or loads (& 2) folded onto its
   // first 2^LOG2 rows (8 MB each at 2^18 lanes), which stay on die -- those accesses without their
@@ -645,6 +557,7 @@ __global__ void __launch_bounds__((walk_threads<MODE, H>()), (walk_blocks_per_cu
   // walk against the blocked layer 1 (kind 4) and -m xpoint against the blocked target filter (kind 3)
   constexpr bool DEFER = MODE == KM_BSGSB || MODE == KM_XPOINTB;
   constexpr uint32_t DKIND = MODE == KM_BSGSB ? 4u : 3u;
+  static_assert(!DEFER || SPARSE, "the deferred-probe forward pass stores the even prefix products only");
   auto drec = [&](const fe &x) -> uint4 {
     if constexpr (MODE == KM_BSGSB) return blk_record(A, x);
     else return tblk_record(A, x);
@@ -670,9 +583,8 @@ __global__ void __launch_bounds__((walk_threads<MODE, H>()), (walk_blocks_per_cu
           acc = dx0;
         else
           fe_mul(acc, acc, dx0);
-        scr_store(scr, slot_w(i), acc, g, L);
+        scr_store(scr, slot_w(i), acc, g, L);  // sparse pad: the even products only
         fe_mul(acc, acc, dx1);
-        if (!SPARSE) scr_store(scr, slot_w(i + 1), acc, g, L);
       }
     } else {
 #pragma unroll 1
@@ -723,44 +635,31 @@ __global__ void __launch_bounds__((walk_threads<MODE, H>()), (walk_blocks_per_cu
     // walk measured 0.2 % slower with it, so it keeps the compares)
     bool wfull = false;
 #if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (MODE == KM_XPOINTB && KH_FULL_GROUPS) wfull = !kh_any(cidx + H > A.n_points);
+    if constexpr (MODE == KM_XPOINTB) wfull = !kh_any(cidx + H > A.n_points);
 #endif
-    // KEEP (sparse pad): the even prefix row last loaded, as its two loaded halves; otherwise `pre`
-    constexpr bool KEEP = SPARSE && KH_SPARSE_KEEP;
-    static_assert(!KEEP || (H % 2) == 0, "the sparse pad pairs odd and even steps");
+    // sparse pad: the even prefix row last loaded, kept as its two loaded halves; dense pad: `pre`
+    static_assert(!SPARSE || (H % 2) == 0, "the sparse pad pairs odd and even steps");
     fe pre;
     pad4 ru, rv;
-    if constexpr (KEEP)
+    if constexpr (SPARSE)
       scr_load_raw(ru, rv, scr, slot(H - 2), g, L);
     else
       scr_load(pre, scr, slot(H - 2), g, L);
-    // one backward step; `par` is the parity of i when the caller knows it (1 odd, 2 even, 0 unknown)
-    auto step = [&](const int i, const int par) __attribute__((always_inline)) {
+    // one backward step; the sparse walks' caller says whether i is odd
+    auto step = [&](const int i, const bool odd) __attribute__((always_inline)) {
       fe tx, ty, di;
-#if KH_PROBE_EARLY
-      // the previous pair's block loads issued before this step's inverse too (they fly during it)
-      uint4 vm, vp;
-      if constexpr (DEFER) {
-        vm = dload(pm);
-        vp = dload(pp);
-      }
-#endif
       ld_tx(tx, i);
       ld_ty(ty, i);
-      if constexpr (KH_TAB_VCOPY && MODE == KM_BSGSB && !LDS) {
-        fe_to_vgpr(tx);  // used by dx and C.x + T.x
-        fe_to_vgpr(ty);  // used by both dy
-      }
       if (i > 0) {
         fe dx;
-        if constexpr (KEEP) {
+        if constexpr (SPARSE) {
           // An odd step i needs the even prefix[i-1], the row R itself, and then loads the next row,
           // prefix[i-3], which serves the two steps after it; an even step rebuilds the odd
           // prefix[i-1] = R * dx[i-1].  R is written by its loads only, so they land in place and
           // fly for a whole step, and each row is read once.
           fe r;
           pad_unpack(r, ru, rv);
-          if (par == 1 || (par == 0 && (i & 1))) {
+          if (odd) {
             fe_mul(di, inv, r);
             if (i > 1) scr_load_raw(ru, rv, scr, slot(i - 3), g, L);
           } else {
@@ -771,7 +670,9 @@ __global__ void __launch_bounds__((walk_threads<MODE, H>()), (walk_blocks_per_cu
             fe_mul(di, inv, p);
           }
         } else {
-          if (SPARSE && ((i - 1) & 1)) {  // prefix[i-1] = prefix[i-2] * dx[i-1] (pre holds prefix[i-2])
+          // Never taken: the walks that reach this arm are dense.  It stays because without it the lambda
+          // captures cx after inv and pre, and the dense walks then allocate their registers differently.
+          if (SPARSE && ((i - 1) & 1)) {
             fe tpx, d1;
             ld_tx(tpx, i - 1);
             fe_sub(d1, tpx, cx);
@@ -790,9 +691,7 @@ __global__ void __launch_bounds__((walk_threads<MODE, H>()), (walk_blocks_per_cu
         // The previous pair's block loads are issued first and tested after this pair's field
         // math: the loads fly during it.  Only their addresses cross the loop edge (ALU values),
         // never an in-flight load destination.
-#if !KH_PROBE_EARLY
         const uint4 vm = dload(pm), vp = dload(pp);
-#endif
         fe xm, xp, s, dy, sx;
         // x3 = s^2 - (C.x + T.x) for both points; dy = -(dy of C - T[i]): only s^2 is needed, so
         // the sign drops out.  Adjacent independent add/sub pairs share one interleaved chain.
@@ -858,16 +757,16 @@ __global__ void __launch_bounds__((walk_threads<MODE, H>()), (walk_blocks_per_cu
         probe_point<MODE>(A, x, y, side ? cidx + off : cidx - off);
       }
     };
-    if constexpr (KEEP) {
+    if constexpr (SPARSE) {
       // two steps per trip, odd then even: the kept row's loads land in place (no copy to wait on)
 #pragma unroll 1
       for (int i = H - 1; i > 0; i -= 2) {
-        step(i, 1);
-        step(i - 1, 2);
+        step(i, true);
+        step(i - 1, false);
       }
     } else {
 #pragma unroll 1
-      for (int i = H - 1; i >= 0; i--) step(i, 0);
+      for (int i = H - 1; i >= 0; i--) step(i, false);
     }
     if constexpr (DEFER) {  // the last pair of the group
       if (plm && blk_match_rec(dload(pm), pm)) record_hit(A, cidx - poff, DKIND);
@@ -992,7 +891,8 @@ __device__ __forceinline__ uint32_t order_limb(int i) {
                          0xFFFFFFFEu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
   return N[i];
 }
-// r = (a + v) mod n for a < n and v = v0 + v1*2^64 + v2*2^128 < n (v2 <= 1)
+// r = (a + v) mod n for a < n and v = v0 + v1*2^64 + v2*2^128 < n (v2 <= 1); one out-of-line copy
+// that k_setup and k_refine call
 __device__ void sc_add_small(uint32_t r[8], const uint32_t a[8], uint64_t v0, uint64_t v1, uint32_t v2) {
   const uint32_t v[8] = {(uint32_t)v0, (uint32_t)(v0 >> 32), (uint32_t)v1, (uint32_t)(v1 >> 32), v2, 0, 0, 0};
   uint32_t c = 0;
@@ -1012,18 +912,13 @@ __device__ void sc_add_small(uint32_t r[8], const uint32_t a[8], uint64_t v0, ui
     for (int i = 0; i < 8; i++) r[i] = subb(r[i], order_limb(i), bo, bo);
   }
 }
-}  // namespace
-
-namespace {
 // r = (a + b) mod n for a, b < n (LE u32 limbs)
 __device__ __forceinline__ void sc_addmod(uint32_t r[8], const uint32_t a[8], const uint32_t b[8]) {
-  const uint32_t N[8] = {0xD0364141u, 0xBFD25E8Cu, 0xAF48A03Bu, 0xBAAEDCE6u,
-                         0xFFFFFFFEu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
   uint32_t t[8], u[8], c = 0, bo = 0;
 #pragma unroll
   for (int i = 0; i < 8; i++) t[i] = addc(a[i], b[i], c, c);
 #pragma unroll
-  for (int i = 0; i < 8; i++) u[i] = subb(t[i], N[i], bo, bo);
+  for (int i = 0; i < 8; i++) u[i] = subb(t[i], order_limb(i), bo, bo);
   // a + b >= n exactly when the sum carried out of 2^256 or the subtraction did not borrow
   const bool ge = c != 0 || bo == 0;
 #pragma unroll
@@ -1518,7 +1413,7 @@ __global__ void k_test_bloom(const uint8_t *items, uint32_t n, uint32_t len, con
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint8_t *p = items + (size_t)i * (len == 32 ? 32 : 20);
-  uint64_t a, b;
+  uint64_t a, b, in[4];  // in: a 32-byte item as xxh64_32 reads it
   if (len < 20) {
     uint32_t w[5];
     load_w5(w, p);
@@ -1536,7 +1431,6 @@ __global__ void k_test_bloom(const uint8_t *items, uint32_t n, uint32_t len, con
     return;
   }
   if (len == 32) {
-    uint64_t in[4];
     for (int k = 0; k < 4; k++) {
       uint64_t v = 0;
       for (int q = 7; q >= 0; q--) v = (v << 8) | p[8 * k + q];
@@ -1546,32 +1440,24 @@ __global__ void k_test_bloom(const uint8_t *items, uint32_t n, uint32_t len, con
     b = xxh64_32(in, a);
   } else {
     uint32_t w[5];
-    for (int k = 0; k < 5; k++)
-      w[k] = (uint32_t)p[4 * k] | ((uint32_t)p[4 * k + 1] << 8) | ((uint32_t)p[4 * k + 2] << 16) |
-             ((uint32_t)p[4 * k + 3] << 24);
+    load_w5(w, p);
     a = xxh64_20(w, KH_BLOOM_SEED);
     b = xxh64_20(w, a);
   }
   const uint8_t *bf = bloom + (sharded ? (size_t)p[0] * bd.stride : 0);
   if (blocked) {
-    // X[8..12), X[12..16), X[16..20), X[20..24) as big-endian u32s (limbs 5, 4, 3, 2)
-    uint32_t w[4];
-    for (int k = 0; k < 4; k++)
+    // X[8..12), X[12..16), X[16..20) as big-endian u32s (limbs 5, 4, 3)
+    uint32_t w[3];
+    for (int k = 0; k < 3; k++)
       w[k] = ((uint32_t)p[8 + 4 * k] << 24) | ((uint32_t)p[9 + 4 * k] << 16) | ((uint32_t)p[10 + 4 * k] << 8) |
              p[11 + 4 * k];
-    out[i] = blk_match(reinterpret_cast<const uint4 *>(bf)[blk_index(w[0], bd)], w[1], w[2], w[3]) ? 1u : 0u;
+    out[i] = blk_match(reinterpret_cast<const uint4 *>(bf)[blk_index(w[0], bd)], w[1], w[2]) ? 1u : 0u;
     if (out_lazy) out_lazy[i] = out[i];  // one probe form only
     return;
   }
   out[i] = bloom_probe(bf, bd, a, b) ? 1u : 0u;
   if (!out_lazy) return;
   if (len == 32) {
-    uint64_t in[4];
-    for (int k = 0; k < 4; k++) {
-      uint64_t v = 0;
-      for (int q = 7; q >= 0; q--) v = (v << 8) | p[8 * k + q];
-      in[k] = v;
-    }
     out_lazy[i] = bloom_probe_lazy(bf, bd, a, [&](uint64_t s) { return xxh64_32(in, s); }) ? 1u : 0u;
   } else {
     walk_args A;
@@ -1597,24 +1483,21 @@ hipError_t launch_walk(int mode, const walk_args &A, hipStream_t st, int H) {
 #ifdef KH_ISA_ONLY_MODE
   // analysis builds (tools/isa_hot.py, tools/valu_mix.py): one large-group walk alone (KH_ISA_ONLY_BSGSB:
   // the BSGS giant walk; KH_ISA_ONLY_MODE=<kh_walk_mode>: any other), compiled in seconds
-  constexpr int TB1 = walk_threads<KH_ISA_ONLY_MODE, KH_WALK_HB>();
-  hipLaunchKernelGGL((k_walk<KH_ISA_ONLY_MODE, KH_WALK_HB>), dim3((A.L + TB1 - 1) / TB1), dim3(TB1), 0, st, A);
+  hipLaunchKernelGGL((k_walk<KH_ISA_ONLY_MODE, KH_WALK_HB>), dim3((A.L + 255) / 256), dim3(256), 0, st, A);
   (void)mode;
   (void)H;
   return hipGetLastError();
 #else
   if (A.zhalf) return launch_walk_zinv(mode, A, st);
   dim3 block(256), grid((A.L + 255) / 256);
-  if (KH_XPOINT_DEFER && mode == KM_XPOINT && A.tblk) mode = KM_XPOINTB;
-  if (KH_H160_BLK && mode == KM_H160C && A.tblk) mode = KM_H160CB;
-  if (KH_H160_BLK && mode == (KM_H160C | KM_P2SH) && A.tblk) mode = KM_H160CB | KM_P2SH;
+  // exact targets: the walks that probe the blocked target filter alone
+  if (mode == KM_XPOINT && A.tblk) mode = KM_XPOINTB;
+  if (mode == KM_H160C && A.tblk) mode = KM_H160CB;
+  if (mode == (KM_H160C | KM_P2SH) && A.tblk) mode = KM_H160CB | KM_P2SH;
   if (H == KH_WALK_HB) {
-    constexpr int TB = walk_threads<KM_BSGSB, KH_WALK_HB>();
     switch (mode) {
       case KM_BSGS: hipLaunchKernelGGL((k_walk<KM_BSGS, KH_WALK_HB>), grid, block, 0, st, A); break;
-      case KM_BSGSB:
-        hipLaunchKernelGGL((k_walk<KM_BSGSB, KH_WALK_HB>), dim3((A.L + TB - 1) / TB), dim3(TB), 0, st, A);
-        break;
+      case KM_BSGSB: hipLaunchKernelGGL((k_walk<KM_BSGSB, KH_WALK_HB>), grid, block, 0, st, A); break;
       case KM_XPOINT: hipLaunchKernelGGL((k_walk<KM_XPOINT, KH_WALK_HB>), grid, block, 0, st, A); break;
       case KM_XPOINTB: hipLaunchKernelGGL((k_walk<KM_XPOINTB, KH_WALK_HB>), grid, block, 0, st, A); break;
       case KM_H160C: hipLaunchKernelGGL((k_walk<KM_H160C, KH_WALK_HB>), grid, block, 0, st, A); break;
@@ -1630,11 +1513,6 @@ hipError_t launch_walk(int mode, const walk_args &A, hipStream_t st, int H) {
     return hipGetLastError();
   }
   if (H != KH_WALK_H) return hipErrorInvalidValue;
-#ifdef KH_ONLY_MODE
-  if (mode != KH_ONLY_MODE) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_walk<KH_ONLY_MODE>, grid, block, 0, st, A);
-  return hipGetLastError();
-#endif
   switch (mode) {
     case KM_H160C: hipLaunchKernelGGL(k_walk<KM_H160C>, grid, block, 0, st, A); break;
     case KM_H160CB: hipLaunchKernelGGL(k_walk<KM_H160CB>, grid, block, 0, st, A); break;

@@ -121,15 +121,12 @@ __device__ __forceinline__ uint32_t kh_lane() {
 }
 #endif
 
-// KH_ADDSUB_MAD: the +-0x1000003D1 fix-up of fe_add / fe_sub on limbs 0..1 as ONE 64-bit
+// The +-0x1000003D1 fix-up of fe_add / fe_sub (device) on limbs 0..1 is ONE 64-bit
 // multiply-add.  0x1000003D1 = 3 * 1431656091, so with a selector s in {0, 3} (add) or {0, -3}
 // (sub, signed v_mad_i64_i32), {r0, r1} + s * 1431656091 is the fix-up mod 2^64; the multiply-add's
 // carry-out (add) or a grown limb 1 (sub: subtracting 0x1000003D1 < 2^33 wraps iff the new limb 1
 // exceeds the old) flags the rare ripple past limb 1 as a lane mask the SALU tests.  Replaces two
 // selects, an add pair and a bool-to-mask round trip per call.
-#ifndef KH_ADDSUB_MAD
-#define KH_ADDSUB_MAD 1
-#endif
 #define KH_P_DIV3 1431656091u
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -149,7 +146,7 @@ __device__ __forceinline__ uint64_t pack64(uint32_t lo, uint32_t hi) { return ((
 #endif
 
 #if defined(__HIP_DEVICE_COMPILE__)
-// The pieces of the KH_ADDSUB_MAD forms.  Tail of an addition: limbs 0..1 of r += c * 0x1000003D1;
+// The pieces of fe_add / fe_sub / fe_addsub2.  Tail of an addition: limbs 0..1 of r += c * 0x1000003D1;
 // m = lanes whose fix-up carries past limb 1; returns the lanes that need fe_add_fix (m, or a top
 // limb of all ones: r may be in [p, 2^256)).
 __device__ __forceinline__ uint64_t fe_add_tail(fe &r, uint32_t c, uint64_t &m) {
@@ -184,31 +181,16 @@ __device__ __forceinline__ void fe_sub_fix(fe &r, uint64_t m) {
 
 KH_HD void fe_add(fe &r, const fe &a, const fe &b) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  if constexpr (KH_ADDSUB_MAD) {
-    uint32_t c = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) r.d[i] = addc(a.d[i], b.d[i], c, c);
-    uint64_t m;
-    if (fe_add_tail(r, c, m) != 0) {
-      KH_RARE_MARK();
-      fe_add_fix(r, m);
-    }
-    return;
-  }
   // a, b < p.  r = a + b; on a carry out of 2^256 (a + b - 2^256 < p) add 2^256 - p = 0x1000003D1:
   // the carry past limb 1 is rare.  Without a carry r < 2^256 is >= p only if its top limb is
   // all ones (rare).
   uint32_t c = 0;
 #pragma unroll
   for (int i = 0; i < 8; i++) r.d[i] = addc(a.d[i], b.d[i], c, c);
-  uint32_t c1;
-  r.d[0] = addc(r.d[0], c ? 0x3D1u : 0u, 0, c1);
-  r.d[1] = addc(r.d[1], c, c1, c1);
-  if (kh_any(c1 != 0 || r.d[7] == 0xFFFFFFFFu)) {
+  uint64_t m;
+  if (fe_add_tail(r, c, m) != 0) {
     KH_RARE_MARK();
-#pragma unroll
-    for (int i = 2; i < 8; i++) r.d[i] = addc(r.d[i], 0, c1, c1);
-    fe_canon(r);
+    fe_add_fix(r, m);
   }
 #else
   uint32_t c = 0;
@@ -231,33 +213,20 @@ KH_HD void fe_sub(fe &r, const fe &a, const fe &b) {
 #pragma unroll
   for (int i = 0; i < 8; i++) r.d[i] = subb(a.d[i], b.d[i], br, br);
 #if defined(__HIP_DEVICE_COMPILE__)
-  if constexpr (KH_ADDSUB_MAD) {
-    const uint64_t m = fe_sub_tail(r, br);
-    if (m != 0) {
-      KH_RARE_MARK();
-      fe_sub_fix(r, m);
-    }
-    return;
-  }
   // borrow: r += p == r -= 0x1000003D1 (mod 2^256); the borrow past limb 1 is rare
-  {
-    uint32_t b2;
-    r.d[0] = subb(r.d[0], br ? 0x3D1u : 0u, 0, b2);
-    r.d[1] = subb(r.d[1], br, b2, b2);
-    if (kh_any(b2 != 0)) {
-      KH_RARE_MARK();
-#pragma unroll
-      for (int i = 2; i < 8; i++) r.d[i] = subb(r.d[i], 0, b2, b2);
-    }
-    return;
+  const uint64_t m = fe_sub_tail(r, br);
+  if (m != 0) {
+    KH_RARE_MARK();
+    fe_sub_fix(r, m);
   }
-#endif
+#else
   // borrow: r += p  == r -= 0x1000003D1 (mod 2^256)
   uint32_t k0 = br ? 0x3D1u : 0u, k1 = br ? 1u : 0u, b2;
   r.d[0] = subb(r.d[0], k0, 0, b2);
   r.d[1] = subb(r.d[1], k1, b2, b2);
 #pragma unroll
   for (int i = 2; i < 8; i++) r.d[i] = subb(r.d[i], 0, b2, b2);
+#endif
 }
 KH_HD void fe_neg(fe &r, const fe &a) {
   fe z;
@@ -266,39 +235,34 @@ KH_HD void fe_neg(fe &r, const fe &a) {
 }
 
 // r = a (+|-) b and q = x (+|-) y (SUB1 / SUB2 pick subtraction), two independent operations with
-// their carry chains interleaved limb by limb (KH_CHAIN2): each chain's next link reads a carry
+// their carry chains interleaved limb by limb on the device: each chain's next link reads a carry
 // the other chain's link separates from its write, filling the pad a lone chain needs per link.
 // Same results as the two single calls; r may alias a or b, q may alias x or y (never across).
-#ifndef KH_CHAIN2
-#define KH_CHAIN2 1
-#endif
 template <bool SUB1, bool SUB2>
 KH_HD void fe_addsub2(fe &r, const fe &a, const fe &b, fe &q, const fe &x, const fe &y) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  if constexpr (KH_ADDSUB_MAD && KH_CHAIN2) {
-    uint32_t c = 0, d = 0;
+  uint32_t c = 0, d = 0;
 #pragma unroll
-    for (int i = 0; i < 8; i++) {
-      r.d[i] = SUB1 ? subb(a.d[i], b.d[i], c, c) : addc(a.d[i], b.d[i], c, c);
-      q.d[i] = SUB2 ? subb(x.d[i], y.d[i], d, d) : addc(x.d[i], y.d[i], d, d);
-    }
-    uint64_t m1 = 0, m2 = 0, f1, f2;
-    if constexpr (SUB1) f1 = fe_sub_tail(r, c); else f1 = fe_add_tail(r, c, m1);
-    if constexpr (SUB2) f2 = fe_sub_tail(q, d); else f2 = fe_add_tail(q, d, m2);
-    if ((f1 | f2) != 0) {
-      KH_RARE_MARK();
-      if (f1 != 0) {
-        if constexpr (SUB1) fe_sub_fix(r, f1); else fe_add_fix(r, m1);
-      }
-      if (f2 != 0) {
-        if constexpr (SUB2) fe_sub_fix(q, f2); else fe_add_fix(q, m2);
-      }
-    }
-    return;
+  for (int i = 0; i < 8; i++) {
+    r.d[i] = SUB1 ? subb(a.d[i], b.d[i], c, c) : addc(a.d[i], b.d[i], c, c);
+    q.d[i] = SUB2 ? subb(x.d[i], y.d[i], d, d) : addc(x.d[i], y.d[i], d, d);
   }
-#endif
+  uint64_t m1 = 0, m2 = 0, f1, f2;
+  if constexpr (SUB1) f1 = fe_sub_tail(r, c); else f1 = fe_add_tail(r, c, m1);
+  if constexpr (SUB2) f2 = fe_sub_tail(q, d); else f2 = fe_add_tail(q, d, m2);
+  if ((f1 | f2) != 0) {
+    KH_RARE_MARK();
+    if (f1 != 0) {
+      if constexpr (SUB1) fe_sub_fix(r, f1); else fe_add_fix(r, m1);
+    }
+    if (f2 != 0) {
+      if constexpr (SUB2) fe_sub_fix(q, f2); else fe_add_fix(q, m2);
+    }
+  }
+#else
   if constexpr (SUB1) fe_sub(r, a, b); else fe_add(r, a, b);
   if constexpr (SUB2) fe_sub(q, x, y); else fe_add(q, x, y);
+#endif
 }
 
 // 512-bit t (16 limbs) -> canonical r.  t = lo + hi*2^256 == lo + hi*(2^32 + 977) (mod p).
@@ -345,47 +309,9 @@ KH_HD void fe_reduce512_gen(fe &r, const uint32_t t[16]) {
 #endif
 }
 
-#if defined(__HIP_DEVICE_COMPILE__)
-// acc += a*b with the 64-bit carry-out of v_mad_u64_u32 counted into cnt (product scanning).
-// The carry lands in an SGPR lane mask and is folded by v_addc_co_u32.
-__device__ __forceinline__ uint64_t mad_acc(uint32_t a, uint32_t b, uint64_t acc, uint32_t &cnt) {
-  uint64_t d, m, junk;
-  asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(d), "=s"(m) : "v"(a), "v"(b), "v"(acc));
-  uint32_t o;
-#ifdef KH_TIMING_EXTRA_NOPS
-  // timing-only build (same results): one more s_nop per carry count prices the hazard pads
-  asm("v_addc_co_u32 %0, %1, 0, %2, %3\n s_nop 1" : "=v"(o), "=s"(junk) : "v"(cnt), "s"(m));
-#else
-  asm("v_addc_co_u32 %0, %1, 0, %2, %3" : "=v"(o), "=s"(junk) : "v"(cnt), "s"(m));
-#endif
-  cnt = o;
-  return d;
-}
-#endif
-
-#if defined(__HIP_DEVICE_COMPILE__)
-// acc + a*b where the sum provably fits 64 bits (no carry to count)
-__device__ __forceinline__ uint64_t mad_nc(uint32_t a, uint32_t b, uint64_t acc) {
-  uint64_t d, m;
-  asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(d), "=s"(m) : "v"(a), "v"(b), "v"(acc));
-  return d;
-}
-#endif
-#ifndef KH_SAFE_ADDC
-#define KH_SAFE_ADDC 1
-#endif
-#ifndef KH_RED2
-#define KH_RED2 1
-#endif
-// KH_COLS: fe_mul / fe_sqr columns as one scheduled asm statement each (kh_cols.h, tools/gen_cols.py)
-#ifndef KH_COLS
-#define KH_COLS 1
-#endif
-// KH_MULRED: fe_mul's reduction slices and chain links issued inside its last column statements
-// (kh_cols.h mul_red_cols), so the chain's carries wait behind column work instead of s_nop pads
-#ifndef KH_MULRED
-#define KH_MULRED 1
-#endif
+// fe_mul / fe_sqr columns (device): one scheduled asm statement each, fe_mul's with its reduction
+// slices and chain links issued inside its last column statements, so the chain's carries wait behind
+// column work instead of s_nop pads (kh_cols.h, tools/gen_cols.py)
 #include "kh_cols.h"
 
 // The fold with 64-bit multiply-adds only (device): with h = t[8..15], l = t[0..7],
@@ -450,73 +376,42 @@ __device__ __forceinline__ void fe_reduce_tail(fe &r, uint32_t R[9], uint64_t m0
 
 KH_HD void fe_reduce512(fe &r, const uint32_t t[16]) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  if constexpr (KH_RED2) {
-    const uint32_t K = 977u;
-    uint64_t m0, m1, m2, m3, m4, m5, m6, m7;
-    const uint64_t V0 = mad_co(t[8], K, pack64(t[0], t[1]), m0);
-    const uint64_t W1 = mad_co(t[9], K, pack64(t[8], t[9]), m1);
-    const uint64_t V2 = mad_co(t[10], K, pack64(t[2], t[3]), m2);
-    const uint64_t W3 = mad_co(t[11], K, pack64(t[10], t[11]), m3);
-    const uint64_t V4 = mad_co(t[12], K, pack64(t[4], t[5]), m4);
-    const uint64_t W5 = mad_co(t[13], K, pack64(t[12], t[13]), m5);
-    const uint64_t V6 = mad_co(t[14], K, pack64(t[6], t[7]), m6);
-    const uint64_t W7 = mad_co(t[15], K, pack64(t[14], t[15]), m7);
-    uint32_t R[9], c, R9;
-    R[0] = (uint32_t)V0;
-    R[1] = addc((uint32_t)(V0 >> 32), (uint32_t)W1, 0, c);
-    R[2] = addc((uint32_t)V2, (uint32_t)(W1 >> 32), c, c);
-    R[3] = addc((uint32_t)(V2 >> 32), (uint32_t)W3, c, c);
-    R[4] = addc((uint32_t)V4, (uint32_t)(W3 >> 32), c, c);
-    R[5] = addc((uint32_t)(V4 >> 32), (uint32_t)W5, c, c);
-    R[6] = addc((uint32_t)V6, (uint32_t)(W5 >> 32), c, c);
-    R[7] = addc((uint32_t)(V6 >> 32), (uint32_t)W7, c, c);
-    R[8] = addc((uint32_t)(W7 >> 32), 0, c, R9);
-    fe_reduce_tail(r, R, m0, m1, m2, m3, m4, m5, m6, m7, [&]() { return R9; });
-    return;
-  }
-#endif
+  const uint32_t K = 977u;
+  uint64_t m0, m1, m2, m3, m4, m5, m6, m7;
+  const uint64_t V0 = mad_co(t[8], K, pack64(t[0], t[1]), m0);
+  const uint64_t W1 = mad_co(t[9], K, pack64(t[8], t[9]), m1);
+  const uint64_t V2 = mad_co(t[10], K, pack64(t[2], t[3]), m2);
+  const uint64_t W3 = mad_co(t[11], K, pack64(t[10], t[11]), m3);
+  const uint64_t V4 = mad_co(t[12], K, pack64(t[4], t[5]), m4);
+  const uint64_t W5 = mad_co(t[13], K, pack64(t[12], t[13]), m5);
+  const uint64_t V6 = mad_co(t[14], K, pack64(t[6], t[7]), m6);
+  const uint64_t W7 = mad_co(t[15], K, pack64(t[14], t[15]), m7);
+  uint32_t R[9], c, R9;
+  R[0] = (uint32_t)V0;
+  R[1] = addc((uint32_t)(V0 >> 32), (uint32_t)W1, 0, c);
+  R[2] = addc((uint32_t)V2, (uint32_t)(W1 >> 32), c, c);
+  R[3] = addc((uint32_t)(V2 >> 32), (uint32_t)W3, c, c);
+  R[4] = addc((uint32_t)V4, (uint32_t)(W3 >> 32), c, c);
+  R[5] = addc((uint32_t)(V4 >> 32), (uint32_t)W5, c, c);
+  R[6] = addc((uint32_t)V6, (uint32_t)(W5 >> 32), c, c);
+  R[7] = addc((uint32_t)(V6 >> 32), (uint32_t)W7, c, c);
+  R[8] = addc((uint32_t)(W7 >> 32), 0, c, R9);
+  fe_reduce_tail(r, R, m0, m1, m2, m3, m4, m5, m6, m7, [&]() { return R9; });
+#else
   fe_reduce512_gen(r, t);
+#endif
 }
 
 KH_HD void fe_mul(fe &r, const fe &a, const fe &b) {
-  uint32_t t[16];
 #if defined(__HIP_DEVICE_COMPILE__)
-  if constexpr (KH_COLS && KH_RED2 && KH_MULRED) {
-    // the columns with the reduction's slices and first chain links interleaved (kh_cols.h)
-    uint32_t R[9];
-    uint64_t mk[8], r9;
-    mul_red_cols(a.d, b.d, R, mk, r9);
-    (void)t;
-    fe_reduce_tail(r, R, mk[0], mk[1], mk[2], mk[3], mk[4], mk[5], mk[6], mk[7],
-                   [&]() { return (uint32_t)(r9 >> kh_lane()) & 1u; });
-    return;
-  }
-  if constexpr (KH_COLS) {
-    mul_cols(a.d, b.d, t);  // the same columns, one scheduled asm statement each (kh_cols.h)
-    fe_reduce512(r, t);
-    return;
-  }
-  // product scanning: column k = sum_{i+j=k} a_i*b_j in a 64-bit accumulator + carry count
-  uint64_t acc = 0;
-  uint32_t cnt = 0;
-#pragma unroll
-  for (int k = 0; k < 15; k++) {
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      const int j = k - i;
-      if (j < 0 || j > 7) continue;
-      // column 0 and the first product of column 1 cannot carry: (2^32-1)^2 + 2^32 - 1 < 2^64
-      if (KH_SAFE_ADDC && (k == 0 || (k == 1 && i == 0)))
-        acc = mad_nc(a.d[i], b.d[j], acc);
-      else
-        acc = mad_acc(a.d[i], b.d[j], acc, cnt);
-    }
-    t[k] = (uint32_t)acc;
-    acc = (acc >> 32) | ((uint64_t)cnt << 32);
-    cnt = 0;
-  }
-  t[15] = (uint32_t)acc;
+  // the columns with the reduction's slices and first chain links interleaved (kh_cols.h)
+  uint32_t R[9];
+  uint64_t mk[8], r9;
+  mul_red_cols(a.d, b.d, R, mk, r9);
+  fe_reduce_tail(r, R, mk[0], mk[1], mk[2], mk[3], mk[4], mk[5], mk[6], mk[7],
+                 [&]() { return (uint32_t)(r9 >> kh_lane()) & 1u; });
 #else
+  uint32_t t[16];
   {
     uint64_t c = 0;
     for (int j = 0; j < 8; j++) {
@@ -535,40 +430,16 @@ KH_HD void fe_mul(fe &r, const fe &a, const fe &b) {
     }
     t[i + 8] = (uint32_t)c;
   }
-#endif
   fe_reduce512(r, t);
+#endif
 }
 
 KH_HD void fe_sqr(fe &r, const fe &a) {
   uint32_t t[16];
 #if defined(__HIP_DEVICE_COMPILE__)
-  // cross products a_i*a_j (i<j) by product scanning, doubled, plus the squares a_i^2
-  if constexpr (KH_COLS) {
-    sqr_cross_cols(a.d, t);  // one scheduled asm statement per column (kh_cols.h)
-  } else {
-  uint64_t acc = 0;
-  uint32_t cnt = 0;
-  t[0] = 0;
-#pragma unroll
-  for (int k = 1; k < 14; k++) {
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      const int j = k - i;
-      if (j <= i || j > 7) continue;
-      // columns 1 and 2 hold one cross product each and column 3 starts on an accumulator of at
-      // most 2^32 - 1: their first products cannot carry
-      if (KH_SAFE_ADDC && k <= 3 && i == 0)
-        acc = mad_nc(a.d[i], a.d[j], acc);
-      else
-        acc = mad_acc(a.d[i], a.d[j], acc, cnt);
-    }
-    t[k] = (uint32_t)acc;
-    acc = (acc >> 32) | ((uint64_t)cnt << 32);
-    cnt = 0;
-  }
-  t[14] = (uint32_t)acc;
-  t[15] = (uint32_t)(acc >> 32);
-  }
+  // cross products a_i*a_j (i<j), one scheduled asm statement per column (kh_cols.h), doubled, plus
+  // the squares a_i^2
+  sqr_cross_cols(a.d, t);
   // double
 #pragma unroll
   for (int i = 15; i > 0; i--) t[i] = __builtin_amdgcn_alignbit(t[i], t[i - 1], 31);
@@ -847,9 +718,6 @@ KH_HD uint32_t bitop3_logic(uint32_t a, uint32_t b, uint32_t c) {
     }
   return r;
 }
-#ifndef KH_BITOP3_FOLD
-#define KH_BITOP3_FOLD 1
-#endif
 template <uint32_t IMM>
 KH_HD uint32_t bitop3(uint32_t a, uint32_t b, uint32_t c) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -857,16 +725,16 @@ KH_HD uint32_t bitop3(uint32_t a, uint32_t b, uint32_t c) {
   // rounds, sigma of the zero schedule words, RIPEMD-160's first steps) goes through plain logic,
   // which LLVM folds; asm would pin each constant in a VGPR and keep the instruction.
   // __builtin_constant_p is resolved after inlining and unrolling (llvm.is.constant).
-  if (KH_BITOP3_FOLD && __builtin_constant_p(a) && __builtin_constant_p(b) && __builtin_constant_p(c))
+  if (__builtin_constant_p(a) && __builtin_constant_p(b) && __builtin_constant_p(c))
     return bitop3_logic<IMM>(a, b, c);
   uint32_t r;
   // one constant operand may come from an SGPR (the VOP3 constant-bus allows one scalar read): the
   // hash IVs of the first rounds then cost no VGPR across the walk's loop
-  if (KH_BITOP3_FOLD && __builtin_constant_p(c))
+  if (__builtin_constant_p(c))
     asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:%4" : "=v"(r) : "v"(a), "v"(b), "s"(c), "i"(IMM));
-  else if (KH_BITOP3_FOLD && __builtin_constant_p(b))
+  else if (__builtin_constant_p(b))
     asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:%4" : "=v"(r) : "v"(a), "s"(b), "v"(c), "i"(IMM));
-  else if (KH_BITOP3_FOLD && __builtin_constant_p(a))
+  else if (__builtin_constant_p(a))
     asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:%4" : "=v"(r) : "s"(a), "v"(b), "v"(c), "i"(IMM));
   else
     asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:%4" : "=v"(r) : "v"(a), "v"(b), "v"(c), "i"(IMM));

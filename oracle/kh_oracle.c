@@ -1195,7 +1195,7 @@ int or_bsgs_refine(const or_bsgs_params *p, const uint8_t *bf2, const uint8_t *b
 }
 
 /* The engine's blocked layer 1 (its own layout, in place of the reference's layer-1 bloom_check
- * of keyhunt.cpp:4819-4822; specified in keyhunt_amd/csrc/kh_kernels.h, KH_PK_MASKS, restated
+ * of keyhunt.cpp:4819-4822; specified in keyhunt_amd/csrc/kh_kernels.h (kh_blk_masks), restated
  * here independently of the device code): shard X[0] holds `blocks` 16-byte blocks; the item's
  * block is (u * blocks) >> 32 with u the big-endian u32 X[8..12); little-endian block word w must
  * cover, with s the big-endian u32 X[12 + 4*(w/2) ..), a = s >> 8*(w%2) and b = a >> 4, the bits

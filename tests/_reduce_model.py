@@ -1,4 +1,4 @@
-"""Python model of the device's 512 -> 256-bit reduction (kh_math.h fe_reduce512, KH_RED2): the
+"""Python model of the device's 512 -> 256-bit reduction (kh_math.h fe_reduce512 and fe_reduce_tail): the
 fast path (V_j / W_i multiply-adds, one carry chain, second fold) with the conditions that send a
 wave to the rare block, and the rare block itself; plus operand pairs whose products overflow each
 V_j / W_i (tests/test_reduce_model.py checks the model on the CPU, tests/test_gpu_primitives.py

@@ -106,7 +106,7 @@ if __name__ == "__main__":
 
 
 def pk128_masks(s0: np.ndarray, s1: np.ndarray):
-    """Masks of the packed-shift layout (kh_kernels.h kh_blk_masks, KH_PK_MASKS): word w gets, from
+    """Masks of the packed-shift layout (kh_kernels.h kh_blk_masks): word w gets, from
     s = s_{w/2}, a = s >> 8*(w%2) and b = a >> 4, bits a & 15, 16 + (a >> 16 & 15), b & 15, 16 + (b >> 16 & 15)."""
     masks = []
     for w in range(4):

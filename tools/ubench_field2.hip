@@ -137,6 +137,16 @@ __device__ __forceinline__ void f29_sqr(f29 &r, const f29 &a) {
 }
 
 // ------------------------------------------------------------------ interleaved pair, 8 x 32
+// acc += a*b with the 64-bit carry-out of v_mad_u64_u32 counted into cnt (product scanning): the
+// carry lands in an SGPR lane mask and is folded by v_addc_co_u32
+__device__ __forceinline__ uint64_t mad_cnt(uint32_t a, uint32_t b, uint64_t acc, uint32_t &cnt) {
+  uint64_t d, m, junk;
+  asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(d), "=s"(m) : "v"(a), "v"(b), "v"(acc));
+  uint32_t o;
+  asm("v_addc_co_u32 %0, %1, 0, %2, %3" : "=v"(o), "=s"(junk) : "v"(cnt), "s"(m));
+  cnt = o;
+  return d;
+}
 __device__ __forceinline__ void fe_mul2(fe &r1, const fe &a1, const fe &b1, fe &r2, const fe &a2, const fe &b2) {
 #if defined(__HIP_DEVICE_COMPILE__)
   uint32_t t1[16], t2[16];
@@ -148,8 +158,8 @@ __device__ __forceinline__ void fe_mul2(fe &r1, const fe &a1, const fe &b1, fe &
     for (int i = 0; i < 8; i++) {
       const int j = k - i;
       if (j < 0 || j > 7) continue;
-      acc1 = mad_acc(a1.d[i], b1.d[j], acc1, cnt1);
-      acc2 = mad_acc(a2.d[i], b2.d[j], acc2, cnt2);
+      acc1 = mad_cnt(a1.d[i], b1.d[j], acc1, cnt1);
+      acc2 = mad_cnt(a2.d[i], b2.d[j], acc2, cnt2);
     }
     t1[k] = (uint32_t)acc1;
     acc1 = (acc1 >> 32) | ((uint64_t)cnt1 << 32);
