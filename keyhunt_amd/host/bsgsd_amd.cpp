@@ -31,7 +31,6 @@
 #include <arpa/inet.h>
 #include <ctype.h>
 #include <errno.h>
-#include <fcntl.h>
 #include <getopt.h>
 #include <netinet/in.h>
 #include <signal.h>
@@ -50,6 +49,7 @@
 #include <vector>
 
 #include "kh_gpu.h"
+#include "kh_bsgs_files.h"
 #include "kh_host_util.h"
 #include "kh_mapped.h"
 
@@ -89,35 +89,10 @@ bool send_all(int fd, const char *buf, size_t len) {
   return true;
 }
 
-std::string tbl_name(const kh_bsgs_info &I) {
-  char f[96];
-  snprintf(f, sizeof f, "keyhunt_bsgs_2_%llu.tbl", (unsigned long long)I.m3);
-  return f;
-}
-
-bool files_present(const kh_bsgs_info &I) {
+bool files_present(const bsgs_names &nm) {
   if (opt.mapped) return false;  // -S files are skipped with --mapped (bsgsd.cpp:1465, 1991)
-  char f[3][96];
-  snprintf(f[0], 96, "keyhunt_bsgs_4_%llu.blm", (unsigned long long)I.m);
-  snprintf(f[1], 96, "keyhunt_bsgs_6_%llu.blm", (unsigned long long)I.m2);
-  snprintf(f[2], 96, "keyhunt_bsgs_7_%llu.blm", (unsigned long long)I.m3);
-  for (auto &x : f)
-    if (access(x, R_OK) != 0) return false;
-  return access(tbl_name(I).c_str(), R_OK) == 0;
-}
-
-// MD5 of `path` into path.md5, reporting an earlier one (bsgsd.cpp:1444-1462, 1648-1665)
-bool md5_refresh(const std::string &path, uint8_t md5[16], bool report) {
-  const std::string md5_path = path + ".md5";
-  if (!md5_of_file(path.c_str(), md5)) {
-    fprintf(stderr, "[W] Unable to compute MD5 for bP table %s\n", path.c_str());
-    return false;
-  }
-  uint8_t disk[16];
-  if (report && read_md5_file(md5_path.c_str(), disk))
-    printf(memcmp(disk, md5, 16) == 0 ? "[+] bP table MD5 verified (%s)\n" : "[W] bP table MD5 mismatch (%s); refreshing\n",
-           md5_path.c_str());
-  if (!write_md5_file(md5_path.c_str(), md5)) fprintf(stderr, "[W] Unable to write bP table MD5 file %s\n", md5_path.c_str());
+  for (const std::string *f : {&nm.blm4, &nm.blm6, &nm.blm7, &nm.tbl})
+    if (access(f->c_str(), R_OK) != 0) return false;
   return true;
 }
 
@@ -127,87 +102,54 @@ bool md5_refresh(const std::string &path, uint8_t md5[16], bool report) {
 // then writes CACHE_TARGET.md5 / .cache from the rows the target holds AT THAT POINT (a fresh --ptable
 // file still holds zeros), and only then are the tables built and the files written.  `rows` returns
 // the --load-ptable rows for every context.
-int first_tables(gpu &g, std::vector<uint8_t> &rows, bool &present) {
+int first_tables(gpu &g, ptable_rows &rows, bool &present) {
   const kh_bsgs_info &I = g.info;
   const uint64_t bytes = I.m3 * 16;
-  const std::string tbl = tbl_name(I);
+  const bsgs_names nm = bsgs_file_names(I.m, I.m2, I.m3);
+  const std::string &tbl = nm.tbl;
   std::string target;  // bptable_cache_target
-  std::vector<uint8_t> target_rows(bytes, 0);
+  std::vector<uint8_t> held;  // its rows, where a fresh --ptable file holds them
+  const uint8_t *target_rows = nullptr;
   uint8_t md5[16];
   bool md5_ready = false;
   if (opt.ptable) {
     target = opt.ptable;
     if (opt.load_ptable) {
-      FILE *f = fopen(opt.ptable, "rb");
-      if (!f) {
-        fprintf(stderr, "[E] Cannot open bP table file\n");
+      if (const ptable_err e = ptable_load_rows(opt.ptable, bytes, rows)) {
+        fprintf(stderr, "[E] %s\n", e == PT_OPEN  ? "Cannot open bP table file"
+                                    : e == PT_MAP ? "Cannot read bP table file"
+                                                  : "Existing bP table file too small");
         return KH_E_IO;
       }
-      struct stat st;
-      if (fstat(fileno(f), &st) != 0 || (uint64_t)st.st_size < bytes) {
-        fclose(f);
-        fprintf(stderr, "[E] Existing bP table file too small\n");
-        return KH_E_IO;
-      }
-      rows.resize(bytes);
-      const bool ok = bytes == 0 || fread(rows.data(), bytes, 1, f) == 1;
-      fclose(f);
-      if (!ok) {
-        fprintf(stderr, "[E] Cannot read bP table file\n");
-        return KH_E_IO;
-      }
-      target_rows = rows;
+      target_rows = rows.data;
       md5_ready = md5_refresh(opt.ptable, md5, true);
     } else {
-      const uint64_t map_bytes = std::max(bytes, opt.ptable_size);
-      int fd = open(opt.ptable, O_RDWR | O_CREAT, 0600);
-      if (fd < 0) {
-        fprintf(stderr, "[E] Cannot create bP table file\n");
+      ptable_err e = ptable_prepare(opt.ptable, bytes, opt.ptable_size);
+      ptable_rows now;  // what the file holds before the build
+      if (e != PT_OPEN && (e || ptable_load_rows(opt.ptable, bytes, now))) e = PT_RESIZE;
+      if (e) {
+        fprintf(stderr, e == PT_OPEN ? "[E] Cannot create bP table file\n" : "[E] Cannot resize bP table file\n");
         return KH_E_IO;
       }
-      struct stat st;
-      bool ok = fstat(fd, &st) == 0;
-      if (ok && (uint64_t)st.st_size < map_bytes) ok = ftruncate(fd, (off_t)map_bytes) == 0;
-      if (ok && map_bytes < (1ull << 20)) {  // small mappings are zeroed (bsgsd.cpp:1424-1431)
-        std::vector<uint8_t> zero(map_bytes, 0);
-        ok = pwrite(fd, zero.data(), map_bytes, 0) == (ssize_t)map_bytes;
-      }
-      if (ok && bytes) ok = pread(fd, target_rows.data(), bytes, 0) == (ssize_t)bytes;
-      close(fd);
-      if (!ok) {
-        fprintf(stderr, "[E] Cannot resize bP table file\n");
-        return KH_E_IO;
-      }
+      held.assign(now.data, now.data + now.bytes);
+      target_rows = held.data();
     }
   }
-  present = files_present(I);
+  present = files_present(nm);
   if (present) {
     int r = kh_bsgs_load(g.ctx, ".", opt.skip_checksum ? KH_LOAD_SKIP_CHECKSUM : 0);
     if (r) return r;
     if (!opt.ptable) {  // the .tbl was read: it is now the cache target, with its MD5 refreshed
       target = tbl;
       uint64_t got = 0;
-      r = kh_get_bsgs_table(g.ctx, target_rows.data(), I.m3, &got);
+      r = kh_bsgs_table_rows(g.ctx, &target_rows, &got);
       if (r) return r;
       md5_ready = md5_refresh(tbl, md5, true);
     }
   }
   if (opt.ptable_cache && !target.empty()) {
     if (!md5_ready) md5_ready = md5_refresh(target, md5, false);
-    if (md5_ready) {
-      const std::string cache = target + ".cache";
-      const int st = bptable_cache_status(cache.c_str(), md5, I.m3);
-      if (st == 1) {
-        printf("[+] bP table cache hit (%s)\n", cache.c_str());
-      } else {
-        printf(st < 0 ? "[W] bP table cache mismatch (%s); rebuilding\n" : "[I] bP table cache not found (%s); creating\n",
-               cache.c_str());
-        if (bptable_cache_write(cache.c_str(), md5, target_rows.data(), I.m3))
-          printf("[+] bP table cache refreshed (%s)\n", cache.c_str());
-        else
-          printf("[W] Unable to write bP table cache to %s\n", cache.c_str());
-      }
-    }
+    if (md5_ready) bptable_cache_refresh(target, md5, target_rows, I.m3);
   }
   if (!present) {
     const bool had_tbl = access(tbl.c_str(), F_OK) == 0;
@@ -230,19 +172,16 @@ int first_tables(gpu &g, std::vector<uint8_t> &rows, bool &present) {
     md5_refresh(tbl, m, false);
   }
   if (opt.ptable && !opt.load_ptable) {  // the built rows land in the --ptable file
-    std::vector<uint8_t> built(bytes);
+    const uint8_t *built = nullptr;
     uint64_t got = 0;
-    int r = kh_get_bsgs_table(g.ctx, built.data(), I.m3, &got);
+    int r = kh_bsgs_table_rows(g.ctx, &built, &got);
     if (r) return r;
-    int fd = open(opt.ptable, O_RDWR);
-    bool ok = fd >= 0 && (bytes == 0 || pwrite(fd, built.data(), bytes, 0) == (ssize_t)bytes);
-    if (fd >= 0) ok = close(fd) == 0 && ok;
-    if (!ok) {
+    if (!ptable_write_rows(opt.ptable, built, bytes)) {
       fprintf(stderr, "[E] Cannot write bP table file\n");
       return KH_E_IO;
     }
   }
-  if (opt.load_ptable) return kh_bsgs_set_table(g.ctx, rows.data(), I.m3);
+  if (opt.load_ptable) return kh_bsgs_set_table(g.ctx, rows.data, I.m3);
   return KH_OK;
 }
 
@@ -331,15 +270,7 @@ void record_key(const U &key, bool compressed, bool at_base) {
   uint8_t kb[32], pxy[64];
   u_to_be32(key, kb);
   kh_pubkeys(g_gpus[0].ctx, kb, 1, pxy);
-  std::string pub;
-  if (compressed) {
-    uint8_t p = (pxy[63] & 1) ? 3 : 2;
-    pub = hex(&p, 1) + hex(pxy, 32);
-  } else {
-    uint8_t p = 4;
-    pub = hex(&p, 1) + hex(pxy, 64);
-  }
-  const std::string k = u_hex(key);
+  const std::string k = u_hex(key), pub = pubkey_text(pxy, compressed);
   // a key at the very start of a base is caught by the reference's base-point check, whose line
   // ends in two spaces (bsgsd.cpp:2544-2548); the giant-step path prints none (2724)
   printf(at_base ? "[+] Thread Key found privkey %s  \n[+] Publickey %s\n" : "[+] Thread Key found privkey %s\n[+] Publickey %s\n",
@@ -491,7 +422,6 @@ int main(int argc, char **argv) {
   signal(SIGPIPE, SIG_IGN);
   printf("[+] Version 0.2.230519 Satoshi Quest (bsgsd-amd: MI355X engine)\n");
   int c;
-  bool have_n = false;
   static const struct option long_opts[] = {{"ptable", required_argument, 0, 1},
                                            {"ptable-size", required_argument, 0, 2},
                                            {"load-ptable", no_argument, 0, 3},
@@ -512,35 +442,12 @@ int main(int argc, char **argv) {
   // --mapped-size / --bloom-bytes / --create-mapped SIZE, with the k/m/g/t suffixes: the entry count
   // and error bsgsd's bloom_entries_for_bytes gives any size (kh_mapped.h entries_for_bsgsd)
   auto size_override = [](const char *arg) {
-    char *end;
-    uint64_t v = strtoull(arg, &end, 10);
-    if (*end) {
-      switch (tolower(*end)) {
-        case 'k': v *= 1024ull; break;
-        case 'm': v *= 1024ull * 1024ull; break;
-        case 'g': v *= 1024ull * 1024ull * 1024ull; break;
-        case 't': v *= 1024ull * 1024ull * 1024ull * 1024ull; break;
-      }
-    }
-    mapped::entries_for_bsgsd(v, &mapped::cfg.entries, &mapped::cfg.error);
+    mapped::entries_for_bsgsd(parse_size(arg), &mapped::cfg.entries, &mapped::cfg.error);
   };
   while ((c = getopt_long(argc, argv, "6hk:n:t:p:i:g:L:B:", long_opts, nullptr)) != -1) {
     switch (c) {
       case 1: opt.ptable = optarg; break;  // bsgsd.cpp:828-829
-      case 2: {                            // bsgsd.cpp:830-841
-        char *end;
-        uint64_t v = strtoull(optarg, &end, 10);
-        if (*end) {
-          switch (tolower(*end)) {
-            case 'k': v *= 1024ull; break;
-            case 'm': v *= 1024ull * 1024ull; break;
-            case 'g': v *= 1024ull * 1024ull * 1024ull; break;
-            case 't': v *= 1024ull * 1024ull * 1024ull * 1024ull; break;
-          }
-        }
-        opt.ptable_size = v;
-        break;
-      }
+      case 2: opt.ptable_size = parse_size(optarg); break;  // bsgsd.cpp:830-841
       case 3: opt.load_ptable = true; break;
       case 4: opt.ptable_cache = true; break;
       case 5:  // bsgsd.cpp:799-803
@@ -577,11 +484,7 @@ int main(int argc, char **argv) {
         if (!opt.k) opt.k = 1;
         printf("[+] K factor %llu\n", (unsigned long long)opt.k);
         break;
-      case 'n':
-        opt.n = (optarg[0] == '0' && (optarg[1] == 'x' || optarg[1] == 'X')) ? strtoull(optarg + 2, nullptr, 16)
-                                                                             : strtoull(optarg, nullptr, 10);
-        have_n = true;
-        break;
+      case 'n': opt.n = parse_n(optarg); break;
       case 't': break;  // one host thread per GPU
       case 'p': opt.port = atoi(optarg); break;
       case 'i': opt.ip = optarg; break;
@@ -606,7 +509,6 @@ int main(int argc, char **argv) {
         return c == 'h' ? EXIT_SUCCESS : EXIT_FAILURE;
     }
   }
-  (void)have_n;
   if (opt.load_ptable && !opt.ptable) {  // bsgsd.cpp:951-954
     fprintf(stderr, "--load-ptable requires --ptable <file>\n");
     return EXIT_FAILURE;
@@ -625,7 +527,7 @@ int main(int argc, char **argv) {
   if (opt.gpus <= 0) opt.gpus = ndev;
   g_gpus.resize(opt.gpus);
   bool present = false;
-  std::vector<uint8_t> ptable_rows;
+  ptable_rows loaded;  // --load-ptable: the file's rows, every context's table
   // every context holds its own tables and walk pad: before any table is built, the contexts each
   // device will carry must fit its free memory (measured before the first context allocates)
   std::vector<uint64_t> dev_free(ndev, 0);
@@ -639,28 +541,20 @@ int main(int argc, char **argv) {
     if (!r && d == 0) {
       uint64_t need = 0;
       kh_bsgs_memory(g.ctx, &need, nullptr);
-      for (int dev = 0; dev < ndev && dev < opt.gpus; dev++) {
-        const uint64_t per = (uint64_t)(opt.gpus / ndev + (dev < opt.gpus % ndev ? 1 : 0));
-        if (dev_free[dev] && per * need > dev_free[dev]) {
-          fprintf(stderr, "[E] -g %d: %llu context(s) on GPU %d need %.1f GB of device memory (%.1f GB each), "
-                          "%.1f GB are free; use fewer contexts (-g) or a smaller -n / -k\n",
-                  opt.gpus, (unsigned long long)per, dev, per * need / 1e9, need / 1e9, dev_free[dev] / 1e9);
-          return EXIT_FAILURE;
-        }
-      }
+      if (!contexts_fit(opt.gpus, ndev, need, dev_free, "-n / -k")) return EXIT_FAILURE;
     }
     if (!r && d == 0) {
-      r = first_tables(g, ptable_rows, present);
+      r = first_tables(g, loaded, present);
     } else if (!r && opt.mapped) {
       // --mapped skips the -S files (bsgsd.cpp:1465, 1991): the first context built its tables and
       // the shard files; the others build theirs too rather than read any -S file left in the
       // directory by an earlier run
       r = kh_bsgs_build(g.ctx);
-      if (!r && opt.load_ptable) r = kh_bsgs_set_table(g.ctx, ptable_rows.data(), g.info.m3);
+      if (!r && opt.load_ptable) r = kh_bsgs_set_table(g.ctx, loaded.data, g.info.m3);
     } else if (!r) {  // the first context left the four files (or the --ptable rows) for the others
       r = kh_bsgs_load(g.ctx, ".", opt.skip_checksum ? KH_LOAD_SKIP_CHECKSUM : 0);
       if (r == KH_E_IO) r = kh_bsgs_build(g.ctx);  // --load-ptable without a .tbl
-      if (!r && opt.load_ptable) r = kh_bsgs_set_table(g.ctx, ptable_rows.data(), g.info.m3);
+      if (!r && opt.load_ptable) r = kh_bsgs_set_table(g.ctx, loaded.data, g.info.m3);
     }
     if (r && mapped::open_failed) return 0;  // a shard file the reference cannot map either: exit(0)
     if (r) {

@@ -12,16 +12,11 @@
 // cache, in the reference's formats) and -B ggsb / --bsgs-block-count / --bsgs-block-size are
 // provided.  Built with -DKH_WITH_MINIKEYS (bin/minikeys-amd) the same source also takes -m minikeys
 // with -C and -8 (thread_process_minikeys, keyhunt.cpp:3094-3259); bin/keyhunt-amd rejects that mode.
-#include <ctype.h>
-#include <fcntl.h>
 #include <getopt.h>
-#include <pthread.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
 #include <time.h>
 #include <unistd.h>
 
@@ -36,6 +31,7 @@
 
 #include "kh_gpu.h"
 #include "../csrc/kh_math.h"
+#include "kh_bsgs_files.h"
 #include "kh_host_util.h"
 #include "kh_mapped.h"
 
@@ -46,71 +42,6 @@ namespace {
 
 const char *VERSION = "keyhunt-amd 0.1 (MI355X engine for keyhunt 0.2.230519 hot paths)";
 
-// ---------------------------------------------------------------------------------------------
-// hashing / encoding for hit output
-// ---------------------------------------------------------------------------------------------
-void sha256(const uint8_t *msg, size_t len, uint8_t out[32]) {
-  uint32_t st[8];
-  sha256_init(st);
-  size_t off = 0;
-  uint32_t w[16];
-  auto load = [&](const uint8_t *b) {
-    for (int i = 0; i < 16; i++)
-      w[i] = ((uint32_t)b[4 * i] << 24) | ((uint32_t)b[4 * i + 1] << 16) | ((uint32_t)b[4 * i + 2] << 8) | b[4 * i + 3];
-  };
-  while (len - off >= 64) {
-    load(msg + off);
-    sha256_transform(st, w);
-    off += 64;
-  }
-  uint8_t blk[128] = {0};
-  size_t rem = len - off;
-  memcpy(blk, msg + off, rem);
-  blk[rem] = 0x80;
-  size_t nb = rem >= 56 ? 2 : 1;
-  uint64_t bits = (uint64_t)len * 8;
-  for (int i = 0; i < 8; i++) blk[nb * 64 - 1 - i] = (uint8_t)(bits >> (8 * i));
-  for (size_t b = 0; b < nb; b++) {
-    load(blk + 64 * b);
-    sha256_transform(st, w);
-  }
-  for (int i = 0; i < 8; i++) {
-    out[4 * i] = st[i] >> 24;
-    out[4 * i + 1] = st[i] >> 16;
-    out[4 * i + 2] = st[i] >> 8;
-    out[4 * i + 3] = st[i];
-  }
-}
-const char *B58 = "123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz";
-std::string b58enc(const uint8_t *d, int n) {
-  std::vector<uint8_t> buf;
-  int zeros = 0;
-  while (zeros < n && d[zeros] == 0) zeros++;
-  for (int i = zeros; i < n; i++) {
-    int carry = d[i];
-    for (auto &b : buf) {
-      carry += b * 256;
-      b = carry % 58;
-      carry /= 58;
-    }
-    while (carry) {
-      buf.push_back(carry % 58);
-      carry /= 58;
-    }
-  }
-  std::string s(zeros, '1');
-  for (auto it = buf.rbegin(); it != buf.rend(); ++it) s += B58[*it];
-  return s;
-}
-std::string rmd_to_address(const uint8_t h[20], uint8_t version = 0) {
-  uint8_t d[25], c1[32], c2[32];
-  d[0] = version;
-  memcpy(d + 1, h, 20);
-  sha256(d, 21, c1);
-  sha256(c1, 32, c2);
-  memcpy(d + 21, c2, 4);
-  return b58enc(d, 25);
-}
 // ---------------------------------------------------------------------------------------------
 // options and shared state
 // ---------------------------------------------------------------------------------------------
@@ -125,7 +56,7 @@ struct options {
   int bits = 0;
   uint64_t kfactor = 1;
   bool flag_n = false;
-  const char *str_n = nullptr;
+  uint64_t n = 0x100000000000ULL;  // -n (keyhunt.cpp:1173-1183: validated in every mode)
   int gpus = 0;
   bool quiet = false;
   int seconds = 30;
@@ -149,14 +80,9 @@ struct options {
   uint64_t ptable_size = 0;
   bool load_ptable = false;
   bool ptable_cache = false;  // --ptable-cache: FILE.md5 + FILE.cache (keyhunt.cpp:1958-1981, 2655-2700)
-  // memory-mapped bloom files (keyhunt.cpp:493-499, 724-806)
-  bool mapped = false;           // FLAGMAPPED
-  bool create_mapped = false;    // FLAGCREATEMAPPED
-  bool load_bloom = false;       // FLAGLOADBLOOM
-  const char *mapped_name = nullptr;
-  uint64_t mapped_entries = 0;   // mapped_entries_override
-  long double mapped_error = 0;  // mapped_error_override
-  uint32_t mapped_chunks = 1;
+  // memory-mapped bloom files (keyhunt.cpp:493-499, 724-806); mapped::cfg holds their other options
+  bool mapped = false;         // FLAGMAPPED
+  bool create_mapped = false;  // FLAGCREATEMAPPED
   int rmd_batch = 1024;  // --rmd-batch-size (keyhunt.cpp:301, 815-829), -m rmd160 only
   bool crypto_given = false;      // -c (FLAGCRYPTO set): no "Setting search for btc" line
   std::string range_start_str, range_end_str;  // -r as typed (BSGS prints them so, keyhunt.cpp:1529-1531)
@@ -184,103 +110,73 @@ U g_end;
 // ---------------------------------------------------------------------------------------------
 // hit output
 // ---------------------------------------------------------------------------------------------
-// nested (--segwit, a KH_KIND_P2SH hit): Address and rmd160 are the P2SH-P2WPKH ones, base58check of
-// 05 || hash160(00 14 || hash160(pubkey)).  Under --segwit a plain compressed hit gets a fifth line,
-// the key's bech32 P2WPKH address.
-void writekey(kh_ctx *ctx, bool compressed, const uint8_t key[32], bool nested = false) {
-  // keyhunt.cpp:6891-6923
-  uint8_t xy[64];
-  kh_pubkeys(ctx, key, 1, xy);
-  fe x, y;
-  fe_from_be(x, xy);
-  fe_from_be(y, xy + 32);
-  uint32_t hw[5];
-  std::string pub;
-  if (compressed) {
-    uint8_t pfx = (y.d[0] & 1) ? 3 : 2;
-    hash160_comp(x, pfx, hw);
-    pub = hex(&pfx, 1) + hex(xy, 32);
-  } else {
-    uint8_t pfx = 4;
-    hash160_uncomp(x, y, hw);
-    pub = hex(&pfx, 1) + hex(xy, 64);
+// What every hit record starts from: the key as GetBase16 prints it, its public key's text and hash160.
+struct hit_text {
+  std::string k, pub;
+  uint8_t xy[64], rmd[20];
+  hit_text(kh_ctx *ctx, const uint8_t key[32], bool compressed) : k(u_hex(u_from_be32(key))) {
+    kh_pubkeys(ctx, key, 1, xy);
+    pub = pubkey_text(xy, compressed);
+    pubkey_hash160(xy, compressed, rmd);
   }
-  uint8_t rmd[20];
-  memcpy(rmd, hw, 20);
-  std::string fifth;
-  if (opt.segwit && compressed && !nested) fifth = "bech32 " + bech32_p2wpkh_encode(rmd) + "\n";
-  if (nested) {
-    uint32_t hn[5];
-    hash160_nested(hw, hn);
-    memcpy(rmd, hn, 20);
-  }
-  std::string addr = rmd_to_address(rmd, nested ? 5 : 0);
-  std::string k = u_hex(u_from_be32(key));
+};
+// the record appended to `file`, and printed after `lead`
+void emit_hit(const char *file, const char *lead, const std::string &text) {
   std::lock_guard<std::mutex> lk(g_keys_mtx);
-  FILE *f = fopen("KEYFOUNDKEYFOUND.txt", "a+");
+  FILE *f = fopen(file, "a+");
   if (f) {
-    fprintf(f, "Private Key: %s\npubkey: %s\nAddress %s\nrmd160 %s\n%s", k.c_str(), pub.c_str(), addr.c_str(),
-            hex(rmd, 20).c_str(), fifth.c_str());
+    fputs(text.c_str(), f);
     fclose(f);
   }
-  printf("\nHit! Private Key: %s\npubkey: %s\nAddress %s\nrmd160 %s\n%s", k.c_str(), pub.c_str(), addr.c_str(),
-         hex(rmd, 20).c_str(), fifth.c_str());
+  printf("%s%s", lead, text.c_str());
   fflush(stdout);
+}
+
+// keyhunt.cpp:6891-6923.  nested (--segwit, a KH_KIND_P2SH hit): Address and rmd160 are the P2SH-P2WPKH
+// ones, base58check of 05 || hash160(00 14 || hash160(pubkey)).  Under --segwit a plain compressed hit gets
+// a fifth line, the key's bech32 P2WPKH address.
+void writekey(kh_ctx *ctx, bool compressed, const uint8_t key[32], bool nested = false) {
+  hit_text h(ctx, key, compressed);
+  std::string fifth;
+  if (opt.segwit && compressed && !nested) fifth = "bech32 " + bech32_p2wpkh_encode(h.rmd) + "\n";
+  if (nested) {
+    uint32_t hw[5], hn[5];
+    memcpy(hw, h.rmd, 20);
+    hash160_nested(hw, hn);
+    memcpy(h.rmd, hn, 20);
+  }
+  emit_hit("KEYFOUNDKEYFOUND.txt", "\nHit! ",
+           "Private Key: " + h.k + "\npubkey: " + h.pub + "\nAddress " + rmd_to_address(h.rmd, nested ? 5 : 0) + "\nrmd160 " +
+               hex(h.rmd, 20) + "\n" + fifth);
 }
 
 // keyhunt.cpp:6925-6950: Ethereum hits
 void writekeyeth(kh_ctx *ctx, const uint8_t key[32]) {
-  uint8_t xy[64];
-  kh_pubkeys(ctx, key, 1, xy);
+  const hit_text h(ctx, key, false);
   fe x, y;
-  fe_from_be(x, xy);
-  fe_from_be(y, xy + 32);
+  fe_from_be(x, h.xy);
+  fe_from_be(y, h.xy + 32);
   uint32_t w[5];
   eth_address(x, y, w);
   uint8_t a[20];
   memcpy(a, w, 20);
-  const std::string k = u_hex(u_from_be32(key)), addr = "0x" + hex(a, 20);
-  std::lock_guard<std::mutex> lk(g_keys_mtx);
-  FILE *f = fopen("KEYFOUNDKEYFOUND.txt", "a+");
-  if (f) {
-    fprintf(f, "Private Key: %s\naddress: %s\n", k.c_str(), addr.c_str());
-    fclose(f);
-  }
-  printf("\n Hit!!!! Private Key: %s\naddress: %s\n", k.c_str(), addr.c_str());
-  fflush(stdout);
+  emit_hit("KEYFOUNDKEYFOUND.txt", "\n Hit!!!! ", "Private Key: " + h.k + "\naddress: 0x" + hex(a, 20) + "\n");
 }
 
 // keyhunt.cpp:6705-6737: vanity hits
 void writevanitykey(kh_ctx *ctx, bool compressed, const uint8_t key[32]) {
-  uint8_t xy[64];
-  kh_pubkeys(ctx, key, 1, xy);
-  fe x, y;
-  fe_from_be(x, xy);
-  fe_from_be(y, xy + 32);
-  uint32_t hw[5];
-  std::string pub;
-  if (compressed) {
-    uint8_t pfx = (y.d[0] & 1) ? 3 : 2;
-    hash160_comp(x, pfx, hw);
-    pub = hex(&pfx, 1) + hex(xy, 32);
-  } else {
-    uint8_t pfx = 4;
-    hash160_uncomp(x, y, hw);
-    pub = hex(&pfx, 1) + hex(xy, 64);
-  }
-  uint8_t rmd[20];
-  memcpy(rmd, hw, 20);
-  const std::string addr = rmd_to_address(rmd), k = u_hex(u_from_be32(key));
-  std::lock_guard<std::mutex> lk(g_keys_mtx);
-  FILE *f = fopen("VANITYKEYFOUND.txt", "a+");
-  if (f) {
-    fprintf(f, "Vanity Private Key: %s\npubkey: %s\nAddress %s\nrmd160 %s\n", k.c_str(), pub.c_str(), addr.c_str(),
-            hex(rmd, 20).c_str());
-    fclose(f);
-  }
-  printf("\nVanity Private Key: %s\npubkey: %s\nAddress %s\nrmd160 %s\n", k.c_str(), pub.c_str(), addr.c_str(),
-         hex(rmd, 20).c_str());
-  fflush(stdout);
+  const hit_text h(ctx, key, compressed);
+  emit_hit("VANITYKEYFOUND.txt", "\n",
+           "Vanity Private Key: " + h.k + "\npubkey: " + h.pub + "\nAddress " + rmd_to_address(h.rmd) + "\nrmd160 " +
+               hex(h.rmd, 20) + "\n");
+}
+
+// keyhunt.cpp:3226-3241: minikey hits (the key through GetBase16: no leading zeros)
+void write_minikey(kh_ctx *ctx, const kh_minikey_hit &m) {
+  const hit_text h(ctx, m.key, false);
+  emit_hit("KEYFOUNDKEYFOUND.txt", "\nHIT!! ",
+           "Private Key: " + h.k + "\npubkey: " + h.pub + "\nminikey: " + m.minikey + "\naddress: " + rmd_to_address(h.rmd) +
+               "\n");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -478,8 +374,8 @@ bool read_targets(const char *fn, int mode, std::vector<uint8_t> &rows, uint64_t
 // top of its bits.  With chunks, the reference's bit -> chunk map (byte / chunk_bytes) equals the
 // concatenation except for bytes past c * chunk_bytes, which it indexes out of bounds.
 // ---------------------------------------------------------------------------------------------
-// the mapped bloom files live in kh_mapped.h (shared with bsgsd-amd); mapped::cfg is filled
-// from the options once they are parsed
+// the mapped bloom files live in kh_mapped.h (shared with bsgsd-amd); parse_options writes their
+// options straight into mapped::cfg
 
 // ---------------------------------------------------------------------------------------------
 // stats (keyhunt.cpp:2850-2962)
@@ -535,6 +431,7 @@ struct addr_job {
   const std::vector<uint8_t> *rows;
   uint64_t bloom_items;
   uint64_t nseq;
+  uint32_t mode = 0;                // the run's kh_scan mode (scan_mode)
   const char *data_file = nullptr;  // -S: data_<hex>.dat to read (or, with save_data, to write)
   bool save_data = false;
   int rc = 0;
@@ -581,6 +478,16 @@ bool write_mapped_data_file(const std::string &path, const mapped::filter &F, co
             fwrite(&data_size, 1, 8, f) == 8 && (data_size == 0 || fwrite(srt.data(), 1, data_size, f) == data_size);
   ok = fclose(f) == 0 && ok;
   return ok;
+}
+
+// The kh_scan mode of the run, from -m, -c eth, -e and --segwit once the targets are read (a 3... target
+// in the file makes every chunk probe the nested digests too): the memory check's, the scan's and its
+// retry's
+uint32_t scan_mode() {
+  const uint32_t mode = opt.mode == MODE_XPOINT                                                  ? KH_MODE_XPOINT
+                        : (opt.eth && (opt.mode == MODE_ADDRESS || opt.mode == MODE_RMD160)) ? KH_MODE_ETH
+                                                                                               : KH_MODE_ADDRESS;
+  return mode | (opt.endo ? KH_MODE_ENDO : 0) | (mode == KH_MODE_ADDRESS && opt.segwit && g_seg_p2sh ? KH_MODE_P2SH : 0);
 }
 
 // a worker's context with the job's targets set (or read from / written to the -S cache)
@@ -643,29 +550,6 @@ void increment_minikey_n(uint8_t raw[21]) {
       raw[i - 1]++;
     }
   raw[0] %= 58;
-}
-
-void write_minikey(kh_ctx *ctx, const kh_minikey_hit &h) {
-  // keyhunt.cpp:3226-3241: the key through GetBase16 (no leading zeros)
-  uint8_t xy[64];
-  kh_pubkeys(ctx, h.key, 1, xy);
-  fe x, y;
-  fe_from_be(x, xy);
-  fe_from_be(y, xy + 32);
-  uint32_t hw[5];
-  hash160_uncomp(x, y, hw);
-  uint8_t rmd[20], pfx = 4;
-  memcpy(rmd, hw, 20);
-  const std::string pub = hex(&pfx, 1) + hex(xy, 64), addr = rmd_to_address(rmd), k = u_hex(u_from_be32(h.key));
-  std::lock_guard<std::mutex> lk(g_keys_mtx);
-  FILE *f = fopen("KEYFOUNDKEYFOUND.txt", "a+");
-  if (f) {
-    fprintf(f, "Private Key: %s\npubkey: %s\nminikey: %s\naddress: %s\n", k.c_str(), pub.c_str(), h.minikey, addr.c_str());
-    fclose(f);
-  }
-  printf("\nHIT!! Private Key: %s\npubkey: %s\nminikey: %s\naddress: %s\n", k.c_str(), pub.c_str(), h.minikey,
-         addr.c_str());
-  fflush(stdout);
 }
 
 void mini_worker(addr_job *j) {
@@ -751,8 +635,6 @@ void addr_worker(addr_job *j) {
   uint8_t st_be[32], stride_be[32];
   u_to_be32(opt.stride, stride_be);
   const U span = u_mul_u64(opt.stride, j->nseq);
-  // --segwit with a 3... target in the file: every chunk also probes the nested digests
-  const uint32_t p2sh = opt.segwit && g_seg_p2sh ? KH_MODE_P2SH : 0;
   while (!r) {
     U base;
     {
@@ -776,15 +658,10 @@ void addr_worker(addr_job *j) {
     }
     u_to_be32(base, st_be);
     uint32_t nh = 0;
-    r = kh_scan(ctx, st_be, stride_be, j->nseq,
-                opt.mode == MODE_XPOINT ? (KH_MODE_XPOINT | (opt.endo ? KH_MODE_ENDO : 0))
-                : (opt.eth && (opt.mode == MODE_ADDRESS || opt.mode == MODE_RMD160)) ? (KH_MODE_ETH | (opt.endo ? KH_MODE_ENDO : 0))
-                      : (KH_MODE_ADDRESS | (opt.endo ? KH_MODE_ENDO : 0) | p2sh),
-                (uint32_t)opt.search, hits.data(), (uint32_t)hits.size(), &nh);
+    r = kh_scan(ctx, st_be, stride_be, j->nseq, j->mode, (uint32_t)opt.search, hits.data(), (uint32_t)hits.size(), &nh);
     if (r == KH_E_OVERFLOW && nh > hits.size()) {  // a short vanity prefix: take them all
       hits.resize(nh);
-      r = kh_scan(ctx, st_be, stride_be, j->nseq, KH_MODE_ADDRESS | (opt.endo ? KH_MODE_ENDO : 0) | p2sh,
-                  (uint32_t)opt.search, hits.data(), (uint32_t)hits.size(), &nh);
+      r = kh_scan(ctx, st_be, stride_be, j->nseq, j->mode, (uint32_t)opt.search, hits.data(), (uint32_t)hits.size(), &nh);
     }
     // KH_E_RANGE (--rmd-batch-size, a group centred on the key 0 mod n): the hits of the groups
     // before it are reported, then the worker stops
@@ -945,45 +822,15 @@ void ptable_md5_loaded() {
   if (read_md5_file(md5_path.c_str(), g_md5)) {
     g_md5_ready = true;
     printf("[+] bP table MD5 loaded (%s)\n", md5_path.c_str());
-  } else if (md5_of_file(opt.ptable, g_md5)) {
-    g_md5_ready = true;
-    uint8_t disk[16];
-    if (read_md5_file(md5_path.c_str(), disk))
-      printf(memcmp(disk, g_md5, 16) == 0 ? "[+] bP table MD5 verified (%s)\n" : "[W] bP table MD5 mismatch (%s); refreshing\n",
-             md5_path.c_str());
-    if (!write_md5_file(md5_path.c_str(), g_md5))
-      fprintf(stderr, "[W] Unable to write bP table MD5 file %s\n", md5_path.c_str());
   } else {
-    fprintf(stderr, "[W] Unable to compute MD5 for bP table %s\n", opt.ptable);
+    g_md5_ready = md5_refresh(opt.ptable, g_md5, true);
   }
 }
 
 void ptable_cache(const uint8_t *rows, uint64_t m3) {
   if (!opt.ptable_cache) return;
-  const std::string md5_path = std::string(opt.ptable) + ".md5", cache_path = std::string(opt.ptable) + ".cache";
-  if (!g_md5_ready) {
-    g_md5_ready = md5_of_file(opt.ptable, g_md5);
-    if (g_md5_ready) {
-      if (!write_md5_file(md5_path.c_str(), g_md5))
-        fprintf(stderr, "[W] Unable to write bP table MD5 file %s\n", md5_path.c_str());
-    } else {
-      fprintf(stderr, "[W] Unable to compute MD5 for bP table %s\n", opt.ptable);
-    }
-  }
-  if (!g_md5_ready) return;
-  const int status = bptable_cache_status(cache_path.c_str(), g_md5, m3);
-  if (status == 1) {
-    printf("[+] bP table cache hit (%s)\n", cache_path.c_str());
-    return;
-  }
-  if (status < 0)
-    printf("[W] bP table cache mismatch (%s); rebuilding\n", cache_path.c_str());
-  else
-    printf("[I] bP table cache not found (%s); creating\n", cache_path.c_str());
-  if (bptable_cache_write(cache_path.c_str(), g_md5, rows, m3))
-    printf("[+] bP table cache refreshed (%s)\n", cache_path.c_str());
-  else
-    printf("[W] Unable to write bP table cache to %s\n", cache_path.c_str());
+  if (!g_md5_ready) g_md5_ready = md5_refresh(opt.ptable, g_md5, false);
+  if (g_md5_ready) bptable_cache_refresh(opt.ptable, g_md5, rows, m3);
 }
 
 // --ptable FILE (keyhunt.cpp:1847-1956): the reference maps FILE (grown to max(M3 x 16 B,
@@ -993,39 +840,22 @@ void ptable_cache(const uint8_t *rows, uint64_t m3) {
 int bsgs_ptable(kh_ctx *ctx, const kh_bsgs_info &info, bool first) {
   if (!opt.ptable) return KH_OK;
   const uint64_t bytes = info.m3 * 16;
+  auto fail = [](const char *what) {
+    fprintf(stderr, "[E] %s\n", what);
+    return KH_E_IO;
+  };
   if (opt.load_ptable) {
-    // the file is mapped read-only, as the reference maps it (keyhunt.cpp:1880-1900), and its first
-    // M3 rows go straight from the mapping into the context's table
-    int fd = open(opt.ptable, O_RDONLY);
-    if (fd < 0) {
-      fprintf(stderr, "[E] Cannot open bP table file\n");
-      return KH_E_IO;
+    // the first M3 rows go straight from the mapping into the context's table
+    ptable_rows map;
+    switch (ptable_load_rows(opt.ptable, bytes, map)) {
+      case PT_OK: break;
+      case PT_OPEN: return fail("Cannot open bP table file");
+      case PT_STAT: return fail("Cannot stat bP table file");
+      case PT_SMALL: return fail("Existing bP table file too small");
+      default: return fail("mmap failed for bP table");
     }
-    struct stat st;
-    if (fstat(fd, &st) != 0) {
-      close(fd);
-      fprintf(stderr, "[E] Cannot stat bP table file\n");
-      return KH_E_IO;
-    }
-    if ((uint64_t)st.st_size < bytes) {
-      close(fd);
-      fprintf(stderr, "[E] Existing bP table file too small\n");
-      return KH_E_IO;
-    }
-    const uint8_t *map = nullptr;
-    if (bytes) {
-      void *m = mmap(nullptr, bytes, PROT_READ, MAP_SHARED, fd, 0);
-      if (m == MAP_FAILED) {
-        close(fd);
-        fprintf(stderr, "[E] mmap failed for bP table\n");
-        return KH_E_IO;
-      }
-      map = (const uint8_t *)m;
-    }
-    close(fd);
-    int r = kh_bsgs_set_table(ctx, map, info.m3);
-    if (!r && first) ptable_cache(map, info.m3);
-    if (map) munmap((void *)map, bytes);
+    int r = kh_bsgs_set_table(ctx, map.data, info.m3);
+    if (!r && first) ptable_cache(map.data, info.m3);
     if (r) fprintf(stderr, "[E] %s\n", kh_last_error(ctx));
     return r;
   }
@@ -1035,35 +865,10 @@ int bsgs_ptable(kh_ctx *ctx, const kh_bsgs_info &info, bool first) {
   uint64_t nrows = 0;
   int r = kh_bsgs_table_rows(ctx, &rows, &nrows);
   if (r) return r;
-  const uint64_t map_bytes = std::max(bytes, opt.ptable_size);
-  int fd = open(opt.ptable, O_RDWR | O_CREAT, 0600);
-  if (fd < 0) {
-    fprintf(stderr, "[E] Cannot create bP table file\n");
-    return KH_E_IO;
-  }
-  struct stat st;
-  bool ok = fstat(fd, &st) == 0;
-  if (ok && (uint64_t)st.st_size < map_bytes) ok = ftruncate(fd, (off_t)map_bytes) == 0;
-  if (!ok) {
-    close(fd);
-    fprintf(stderr, "[E] Cannot resize bP table file\n");
-    return KH_E_IO;
-  }
-  // mappings under 1 MiB are zeroed first (keyhunt.cpp:1941-1951); larger ones keep their bytes
-  if (map_bytes < (1ull << 20)) {
-    std::vector<uint8_t> zero(map_bytes, 0);
-    ok = pwrite(fd, zero.data(), map_bytes, 0) == (ssize_t)map_bytes;
-  }
-  for (uint64_t o = 0; ok && o < bytes;) {
-    ssize_t w = pwrite(fd, rows + o, bytes - o, (off_t)o);
-    ok = w > 0;
-    if (ok) o += (uint64_t)w;
-  }
-  ok = close(fd) == 0 && ok;
-  if (!ok) {
-    fprintf(stderr, "[E] Cannot write bP table file\n");
-    return KH_E_IO;
-  }
+  const ptable_err e = ptable_prepare(opt.ptable, bytes, opt.ptable_size);
+  if (e == PT_OPEN) return fail("Cannot create bP table file");
+  if (e == PT_RESIZE) return fail("Cannot resize bP table file");
+  if (e || !ptable_write_rows(opt.ptable, rows, bytes)) return fail("Cannot write bP table file");
   ptable_cache(rows, info.m3);
   return KH_OK;
 }
@@ -1134,11 +939,10 @@ void setup_wait() {
 // mapped shard filters -- each shard's struct bloom as the mapping left it, its bits and their sha256
 // twice -- and the sorted bP rows with their sha256, in the reference's order 4, 6, 2, 7
 int write_mapped_tables(kh_ctx *ctx, const kh_bsgs_info &info, const std::vector<std::vector<mapped::filter>> &F) {
-  const uint64_t ms[3] = {info.m, info.m2, info.m3};
-  const int kinds[3] = {4, 6, 7};
+  const bsgs_names nm = bsgs_file_names(info.m, info.m2, info.m3);
+  const std::string *blm[3] = {&nm.blm4, &nm.blm6, &nm.blm7};
   auto layer = [&](int l) {
-    char fn[96];
-    snprintf(fn, sizeof fn, "keyhunt_bsgs_%d_%llu.blm", kinds[l], (unsigned long long)ms[l]);
+    const char *fn = blm[l]->c_str();
     FILE *f = fopen(fn, "wb");
     if (!f) {
       fprintf(stderr, "[E] Error can't create the file %s\n", fn);
@@ -1163,8 +967,7 @@ int write_mapped_tables(kh_ctx *ctx, const kh_bsgs_info &info, const std::vector
   uint64_t n = 0;
   int r = kh_bsgs_table_rows(ctx, &rows, &n);
   if (r) return r;
-  char fn[96];
-  snprintf(fn, sizeof fn, "keyhunt_bsgs_2_%llu.tbl", (unsigned long long)info.m3);
+  const char *fn = nm.tbl.c_str();
   FILE *f = fopen(fn, "wb");
   if (!f) {
     fprintf(stderr, "[E] Error can't create the file %s\n", fn);
@@ -1205,12 +1008,12 @@ int bsgs_tables(kh_ctx *ctx, const kh_bsgs_info &info, bool first) {
     if (!r && first) print_build_lines(info);
     return r;
   }
-  char f4[96], f6[96], f7[96], f2[96];
+  const bsgs_names nm = bsgs_file_names(info.m, info.m2, info.m3);
+  const char *f4 = nm.blm4.c_str(), *f6 = nm.blm6.c_str(), *f7 = nm.blm7.c_str(), *f2 = nm.tbl.c_str();
   if (opt.load_ptable) {
     // -S with --load-ptable (keyhunt.cpp:2153-2186): the reference reads the .tbl into its
     // read-only mapping of the --ptable file, which fails, or reports the .tbl missing; it never
     // writes the .tbl (2588)
-    snprintf(f2, sizeof f2, "keyhunt_bsgs_2_%llu.tbl", (unsigned long long)info.m3);
     if (access(f2, F_OK) == 0) {
       fprintf(stderr, "[E] Error reading the file %s\n", f2);
     } else {
@@ -1219,10 +1022,6 @@ int bsgs_tables(kh_ctx *ctx, const kh_bsgs_info &info, bool first) {
     }
     return KH_E_IO;
   }
-  snprintf(f4, sizeof f4, "keyhunt_bsgs_4_%llu.blm", (unsigned long long)info.m);
-  snprintf(f6, sizeof f6, "keyhunt_bsgs_6_%llu.blm", (unsigned long long)info.m2);
-  snprintf(f7, sizeof f7, "keyhunt_bsgs_7_%llu.blm", (unsigned long long)info.m3);
-  snprintf(f2, sizeof f2, "keyhunt_bsgs_2_%llu.tbl", (unsigned long long)info.m3);
   static std::mutex mtx;
   static int decided = 0;  // 1: every worker reads the files, 2: every worker builds, the first writes
   {
@@ -1274,14 +1073,7 @@ bool print_found(kh_ctx *ctx, const bsgs_job *j, const kh_bsgs_found &fd) {
   std::string k = u_hex(u_from_be32(fd.key));
   uint8_t pxy[64];
   kh_pubkeys(ctx, fd.key, 1, pxy);
-  std::string pub;
-  if ((*j->comp)[t]) {
-    uint8_t p = (pxy[63] & 1) ? 3 : 2;
-    pub = hex(&p, 1) + hex(pxy, 32);
-  } else {
-    uint8_t p = 4;
-    pub = hex(&p, 1) + hex(pxy, 64);
-  }
+  const std::string pub = pubkey_text(pxy, (*j->comp)[t]);
   {
     std::lock_guard<std::mutex> lk2(g_keys_mtx);
     // each BSGS worker of the reference has its own format: the sequential one (also -B ggsb and
@@ -1491,14 +1283,19 @@ void usage(const char *p) {
          , p);
 }
 
-}  // namespace
+// ---------------------------------------------------------------------------------------------
+// main's steps
+// ---------------------------------------------------------------------------------------------
+const U ORDER = [] {
+  U o;
+  u_from_hex(ORDER_HEX, o);
+  return o;
+}();
 
-int main(int argc, char **argv) {
-  printf("[+] Version %s\n", VERSION);
+// The command line into opt and mapped::cfg, with the lines the reference prints as it reads each
+// option.  False when the program ends here, with `status`.
+bool parse_options(int argc, char **argv, int &status) {
   const char *mode_names[] = {"address", "rmd160", "xpoint", "bsgs", "vanity", "minikeys"};
-  int c;
-  U order;
-  u_from_hex(ORDER_HEX, order);
   static const struct option long_opts[] = {{"bsgs-block-count", required_argument, 0, 1},
                                            {"bsgs-block-size", required_argument, 0, 2},
                                            {"ptable", required_argument, 0, 3},
@@ -1519,11 +1316,13 @@ int main(int argc, char **argv) {
   // --mapped-size / --bloom-bytes / --create-mapped N: the entry count and error the byte budget
   // allows (bloom_entries_for_bytes, keyhunt.cpp:7510-7530)
   auto size_override = [](uint64_t bytes) {
-    uint64_t n;
     uint32_t k;
-    mapped::entries_for(bytes, &n, &k);
-    opt.mapped_entries = n;
-    opt.mapped_error = powl(0.5L, (long double)k);
+    mapped::entries_for(bytes, &mapped::cfg.entries, &k);
+    mapped::cfg.error = powl(0.5L, (long double)k);
+  };
+  auto fail = [&]() {
+    status = EXIT_FAILURE;
+    return false;
   };
 #ifdef KH_WITH_MINIKEYS
   const char *short_opts = "m:f:l:r:b:k:n:t:g:qs:I:L:MRec:B:S6v:z:dhC:8:";
@@ -1532,6 +1331,7 @@ int main(int argc, char **argv) {
   const char *short_opts = "m:f:l:r:b:k:n:t:g:qs:I:L:MRec:B:S6v:z:dh";
   const int n_modes = 5;
 #endif
+  int c;
   while ((c = getopt_long(argc, argv, short_opts, long_opts, nullptr)) != -1) {
     switch (c) {
 #ifdef KH_WITH_MINIKEYS
@@ -1544,13 +1344,13 @@ int main(int argc, char **argv) {
             const char *p = strchr(alpha, optarg[i + 1]);
             if (!p) {
               fprintf(stderr, "[E] invalid character in minikey\n");
-              return EXIT_FAILURE;
+              return fail();
             }
             g_mk_raw[i] = (uint8_t)((p - alpha) % 58);
           }
         } else {
           fprintf(stderr, "[E] Invalid Minikey length %li : %s\n", (long)strlen(optarg), optarg);
-          return EXIT_FAILURE;
+          return fail();
         }
         break;
       case '8':  // keyhunt.cpp:1102-1110
@@ -1559,7 +1359,7 @@ int main(int argc, char **argv) {
           printf("[+] Base58 for Minikeys %s\n", opt.alphabet);
         } else {
           fprintf(stderr, "[E] The base58 alphabet must be 58 characters long.\n");
-          return EXIT_FAILURE;
+          return fail();
         }
         break;
 #endif
@@ -1571,49 +1371,25 @@ int main(int argc, char **argv) {
         opt.ggsb_size = strtoull(optarg, NULL, 10);
         opt.ggsb = opt.ggsb_size > 0;
         break;
-      case 3: opt.ptable = optarg; break;  // keyhunt.cpp:772-773
-      case 4: {                            // keyhunt.cpp:774-785
-        char *end;
-        uint64_t v = strtoull(optarg, &end, 10);
-        if (*end) {
-          switch (tolower(*end)) {
-            case 'k': v *= 1024ull; break;
-            case 'm': v *= 1024ull * 1024ull; break;
-            case 'g': v *= 1024ull * 1024ull * 1024ull; break;
-            case 't': v *= 1024ull * 1024ull * 1024ull * 1024ull; break;
-          }
-        }
-        opt.ptable_size = v;
-        break;
-      }
-      case 5: opt.load_ptable = true; break;  // keyhunt.cpp:786-787
-      case 6: opt.ptable_cache = true; break;  // keyhunt.cpp:788-789
-      case 7:                                  // keyhunt.cpp:744-748
+      case 3: opt.ptable = optarg; break;                    // keyhunt.cpp:772-773
+      case 4: opt.ptable_size = parse_size(optarg); break;   // keyhunt.cpp:774-785
+      case 5: opt.load_ptable = true; break;                 // keyhunt.cpp:786-787
+      case 6: opt.ptable_cache = true; break;                // keyhunt.cpp:788-789
+      case 7:                                                // keyhunt.cpp:744-748
         opt.mapped = true;
-        if (optarg) opt.mapped_name = optarg;
+        if (optarg) mapped::cfg.name = optarg;
         break;
-      case 8: {  // keyhunt.cpp:749-765, with the k/m/g/t suffixes
+      case 8:  // keyhunt.cpp:749-765, with the k/m/g/t suffixes
         opt.mapped = true;
-        char *end;
-        uint64_t v = strtoull(optarg, &end, 10);
-        if (*end) {
-          switch (tolower(*end)) {
-            case 'k': v *= 1024ull; break;
-            case 'm': v *= 1024ull * 1024ull; break;
-            case 'g': v *= 1024ull * 1024ull * 1024ull; break;
-            case 't': v *= 1024ull * 1024ull * 1024ull * 1024ull; break;
-          }
-        }
-        size_override(v);
+        size_override(parse_size(optarg));
         break;
-      }
       case 9:  // keyhunt.cpp:766-768
         opt.mapped = true;
-        opt.mapped_chunks = (uint32_t)strtoul(optarg, NULL, 10);
+        mapped::cfg.chunks = (uint32_t)strtoul(optarg, NULL, 10);
         break;
-      case 10: opt.mapped_name = optarg; break;  // keyhunt.cpp:768-769 (does not set --mapped)
-      case 11: opt.load_bloom = true; break;     // keyhunt.cpp:770-771
-      case 12:                                   // keyhunt.cpp:790-796
+      case 10: mapped::cfg.name = optarg; break;      // keyhunt.cpp:768-769 (does not set --mapped)
+      case 11: mapped::cfg.load_bloom = true; break;  // keyhunt.cpp:770-771
+      case 12:                                        // keyhunt.cpp:790-796
         opt.mapped = true;
         size_override(strtoull(optarg, NULL, 10));
         break;
@@ -1634,14 +1410,14 @@ int main(int argc, char **argv) {
         opt.rmd_batch = (int)v;
         break;
       }
-      case 16: opt.segwit = true; break;  // -m address: bech32 and P2SH-P2WPKH targets (checked below)
+      case 16: opt.segwit = true; break;  // -m address: bech32 and P2SH-P2WPKH targets (checked in check_options)
       case 'm': {
         int m = -1;
         for (int i = 0; i < n_modes; i++)
           if (!strcmp(optarg, mode_names[i])) m = i;
         if (m < 0) {
           fprintf(stderr, "[E] Unsupported mode %s (engine covers address, rmd160, xpoint, bsgs, vanity)\n", optarg);
-          return EXIT_FAILURE;
+          return fail();
         }
         opt.mode = m;
         if (m != MODE_BSGS) printf("[+] Mode %s\n", optarg);  // BSGS: "[+] Mode BSGS <schedule>" later
@@ -1663,7 +1439,7 @@ int main(int argc, char **argv) {
         if (!strcmp(optarg, "compress")) { opt.search = KH_SEARCH_COMPRESS; printf("[+] Search compress only\n"); }
         else if (!strcmp(optarg, "uncompress")) { opt.search = KH_SEARCH_UNCOMPRESS; printf("[+] Search uncompress only\n"); }
         else if (!strcmp(optarg, "both")) { opt.search = KH_SEARCH_BOTH; printf("[+] Search both compress and uncompress\n"); }
-        else { fprintf(stderr, "[E] Unknow search type %s\n", optarg); return EXIT_FAILURE; }
+        else { fprintf(stderr, "[E] Unknow search type %s\n", optarg); return fail(); }
         break;
       case 'r': {  // keyhunt.cpp:1024-1055: START[:END]; START alone runs to the group order
         std::string s(optarg);
@@ -1690,7 +1466,7 @@ int main(int argc, char **argv) {
         }
         break;
       case 'k': opt.kfactor = strtoull(optarg, nullptr, 10); if (!opt.kfactor) opt.kfactor = 1; printf("[+] K factor %llu\n", (unsigned long long)opt.kfactor); break;
-      case 'n': opt.flag_n = true; opt.str_n = optarg; break;
+      case 'n': opt.flag_n = true; opt.n = parse_n(optarg); break;
       case 't': {  // host threads: one per GPU context here (see -g); echoed as keyhunt.cpp:1076-1082 does
         long t = strtol(optarg, NULL, 10);
         if (t <= 0) t = 1;
@@ -1710,7 +1486,7 @@ int main(int argc, char **argv) {
       case 'I': {
         U s;
         bool ok = (optarg[0] == '0' && optarg[1] == 'x') ? u_from_hex(optarg, s) : u_from_dec(optarg, s);
-        if (!ok || u_is_zero(s)) { fprintf(stderr, "[E] invalid stride %s\n", optarg); return EXIT_FAILURE; }
+        if (!ok || u_is_zero(s)) { fprintf(stderr, "[E] invalid stride %s\n", optarg); return fail(); }
         opt.stride = s;
         opt.stride_set = true;
         break;
@@ -1719,7 +1495,7 @@ int main(int argc, char **argv) {
       case 'L':  // BSGS layer-1 layout on the GPU (engine option; the reference has one layout)
         if (!strcmp(optarg, "reference")) opt.layer1 = KH_LAYER1_REFERENCE;
         else if (!strcmp(optarg, "blocked")) opt.layer1 = KH_LAYER1_BLOCKED;
-        else { fprintf(stderr, "[E] -L reference|blocked\n"); return EXIT_FAILURE; }
+        else { fprintf(stderr, "[E] -L reference|blocked\n"); return fail(); }
         break;
       case 'R':  // keyhunt.cpp:1019-1023
         printf("[+] Random mode\n");
@@ -1756,12 +1532,13 @@ int main(int argc, char **argv) {
           printf("[+] Setting search for ETH adddress.\n");
         } else {
           fprintf(stderr, "[E] Unknow crypto value %s\n", optarg);
-          return EXIT_FAILURE;
+          return fail();
         }
         break;
       case 'z':  // keyhunt.cpp:1112-1118: bloom entries = multiplier x items above 10000 (7608)
         opt.bloom_mult = (int)strtol(optarg, NULL, 10);
         if (opt.bloom_mult <= 0) opt.bloom_mult = 1;
+        mapped::cfg.bloom_mult = opt.bloom_mult;
         printf("[+] Bloom Size Multiplier %i\n", opt.bloom_mult);
         break;
       case 'd':  // keyhunt.cpp:1019-1022
@@ -1769,38 +1546,38 @@ int main(int argc, char **argv) {
         break;
       case 'h':
         usage(argv[0]);
-        return EXIT_SUCCESS;
-      default: usage(argv[0]); return EXIT_FAILURE;
+        status = EXIT_SUCCESS;
+        return false;
+      default: usage(argv[0]); return fail();
     }
   }
   if (opt.load_ptable && !opt.ptable) {  // keyhunt.cpp:1126-1129
     fprintf(stderr, "--load-ptable requires --ptable <file>\n");
-    return EXIT_FAILURE;
+    return fail();
   }
-  mapped::cfg.name = opt.mapped_name;
-  mapped::cfg.chunks = opt.mapped_chunks;
-  mapped::cfg.load_bloom = opt.load_bloom;
-  mapped::cfg.entries = opt.mapped_entries;
-  mapped::cfg.error = opt.mapped_error;
-  mapped::cfg.bloom_mult = opt.bloom_mult;
-  if (opt.create_mapped) return mapped::create();  // keyhunt.cpp:1131-1172: make the file(s) and exit
+  if (opt.create_mapped) {  // keyhunt.cpp:1131-1172: make the file(s) from the whole command line and exit
+    status = mapped::create();
+    return false;
+  }
+  return true;
+}
+
+// The checks on the options together, and the lines that follow them (keyhunt.cpp:1173-1220)
+bool check_options() {
   if (!opt.file && !(opt.mode == MODE_VANITY && opt.vanity.targets)) {
     fprintf(stderr, "[E] -f FILE is required\n");
-    return EXIT_FAILURE;
+    return false;
   }
-  // validate_nk (keyhunt.cpp:1173-1183): applied to every mode
-  uint64_t nk_n = 0x100000000000ULL;
-  if (opt.flag_n) nk_n = (opt.str_n[0] == '0' && (opt.str_n[1] == 'x' || opt.str_n[1] == 'X')) ? strtoull(opt.str_n + 2, nullptr, 16) : strtoull(opt.str_n, nullptr, 10);
-  if (!validate_nk(nk_n, opt.kfactor)) return EXIT_FAILURE;
+  if (!validate_nk(opt.n, opt.kfactor)) return false;  // keyhunt.cpp:1173-1183: applied to every mode
   // keyhunt.cpp:1185-1193 compares the -B index with MODE_BSGS (2), i.e. these two guards fire
   // for -B both whatever -m is (SURVEY 8a parity note 7); BSGS itself ignores -e and -I
   if (opt.bsgs_mode == BM_BOTH && opt.endo) {
     fprintf(stderr, "[E] Endomorphism doesn't work with BSGS\n");
-    return EXIT_FAILURE;
+    return false;
   }
   if (opt.bsgs_mode == BM_BOTH && opt.stride_set) {
     fprintf(stderr, "[E] Stride doesn't work with BSGS\n");
-    return EXIT_FAILURE;
+    return false;
   }
   // --segwit: -m address with compressed keys only, and no -S (the data_<hex>.dat cache keeps no address
   // type, so a run that reads it could not know whether to probe the nested digests)
@@ -1812,23 +1589,27 @@ int main(int argc, char **argv) {
                                                        : nullptr;
     if (why) {
       fprintf(stderr, "[E] %s\n", why);
-      return EXIT_FAILURE;
+      return false;
     }
   }
   if (opt.stride_set) printf("[+] Stride : %s\n", u_dec(opt.stride).c_str());  // keyhunt.cpp:1195-1203
   if (opt.mode == MODE_BSGS) printf("[+] Mode BSGS %s\n", BSGS_MODES[opt.bsgs_mode]);  // keyhunt.cpp:1209-1211
   if (opt.mode == MODE_ADDRESS && !opt.crypto_given) printf("[+] Setting search for btc adddress\n");  // 1217-1220
-  // ranges (keyhunt.cpp:854-873, 1221-1269)
+  return true;
+}
+
+// opt.start / opt.end and the cursors from -b, -r or neither (keyhunt.cpp:854-873, 1221-1269)
+void setup_range() {
   if (opt.have_bits) {
     opt.start = u_shl1(opt.bits - 1);
     opt.end = u_shl1(opt.bits);
-    if (u_cmp(opt.end, order) > 0) opt.end = order;
+    if (u_cmp(opt.end, ORDER) > 0) opt.end = ORDER;
   } else if (opt.have_range) {
     if (u_is_zero(opt.start)) opt.start = u_from_u64(1);
     if (u_cmp(opt.start, opt.end) == 0) {
       fprintf(stderr, "[E] Start and End range can't be the same\nFallback to random mode!\n");
       opt.have_range = false;
-    } else if (u_cmp(opt.start, order) >= 0 || u_cmp(opt.end, order) > 0) {
+    } else if (u_cmp(opt.start, ORDER) >= 0 || u_cmp(opt.end, ORDER) > 0) {
       fprintf(stderr, "[E] Start and End range can't be great than N\nFallback to random mode!\n");
       opt.have_range = false;
     } else {
@@ -1841,325 +1622,347 @@ int main(int argc, char **argv) {
   if (!opt.have_bits && !opt.have_range) {
     // no usable range (keyhunt.cpp:1250-1255, 1534-1540): the address family walks sequentially
     // from 1 to the group order; BSGS starts at a random key below the order and walks up
-    opt.start = opt.mode == MODE_BSGS ? u_rand_range(u_from_u64(1), order) : u_from_u64(1);
-    opt.end = order;
+    opt.start = opt.mode == MODE_BSGS ? u_rand_range(u_from_u64(1), ORDER) : u_from_u64(1);
+    opt.end = ORDER;
   }
-  // the range lines: the address family prints them after "[+] N =" with the range as used
-  // (keyhunt.cpp:1325-1339); BSGS after reading its targets, with -r's strings as typed and nothing
-  // for a random start (1517-1540)
-  auto print_range = [&]() {
-    if (opt.mode == MODE_BSGS && !opt.have_bits && !opt.have_range) return;
-    printf(opt.have_bits ? "[+] Bit Range %d\n" : "[+] Range \n", opt.bits);
-    if (opt.mode == MODE_BSGS && !opt.have_bits)
-      printf("[+] -- from : 0x%s\n[+] -- to   : 0x%s\n", opt.range_start_str.c_str(),
-             opt.range_end_str.empty() ? u_hex(order).c_str() : opt.range_end_str.c_str());
-    else
-      printf("[+] -- from : 0x%s\n[+] -- to   : 0x%s\n", u_hex(opt.start).c_str(), u_hex(opt.end).c_str());
-  };
-  // -g contexts: one host thread + kh_ctx each, on device d % ndev.  More contexts than devices
-  // share a device (as the reference's -t threads share the host's cores); each keeps its own
-  // tables and lanes, and they all take work from the one cursor (keyhunt.cpp:3321-3324, 4600-4617).
-  // The devices are counted once the targets are read, so the reference's lines come first.
-  int ndev = 0, gpus = 0;
-  std::vector<addr_job> aj;
-  std::vector<bsgs_job> bj;
-  auto open_devices = [&]() {
-    kh_device_count(&ndev);
-    if (ndev < 1) {
-      fprintf(stderr, "[E] no GPU found\n");
-      return false;
-    }
-    gpus = opt.gpus > 0 ? opt.gpus : ndev;
-    printf("[+] GPUs : %d (%d context%s)\n", std::min(gpus, ndev), gpus, gpus == 1 ? "" : "s");
-    aj.resize(gpus);
-    bj.resize(gpus);
-    return true;
-  };
   g_cursor = opt.start;
   g_end = opt.end;
   g_top = opt.end;
-  U twoN;
+}
+
+// the range lines: the address family prints them after "[+] N =" with the range as used
+// (keyhunt.cpp:1325-1339); BSGS after reading its targets, with -r's strings as typed and nothing
+// for a random start (1517-1540)
+void print_range() {
+  if (opt.mode == MODE_BSGS && !opt.have_bits && !opt.have_range) return;
+  printf(opt.have_bits ? "[+] Bit Range %d\n" : "[+] Range \n", opt.bits);
+  if (opt.mode == MODE_BSGS && !opt.have_bits)
+    printf("[+] -- from : 0x%s\n[+] -- to   : 0x%s\n", opt.range_start_str.c_str(),
+           opt.range_end_str.empty() ? u_hex(ORDER).c_str() : opt.range_end_str.c_str());
+  else
+    printf("[+] -- from : 0x%s\n[+] -- to   : 0x%s\n", u_hex(opt.start).c_str(), u_hex(opt.end).c_str());
+}
+
+// What the worker threads read until they are joined.
+// -g contexts: one host thread + kh_ctx each, on device d % ndev.  More contexts than devices
+// share a device (as the reference's -t threads share the host's cores); each keeps its own
+// tables and lanes, and they all take work from the one cursor (keyhunt.cpp:3321-3324, 4600-4617).
+struct run {
+  int ndev = 0, gpus = 0;
+  std::vector<addr_job> aj;
+  std::vector<bsgs_job> bj;
   std::vector<std::thread> th;
   std::vector<uint8_t> rows;
-  std::string data_file;  // -S target cache (outlives the GPU threads)
+  std::string data_file;  // -S target cache
   std::vector<fe> tx, ty;
   std::vector<bool> comp;
+  U twoN;
+};
 
-  if (opt.mode != MODE_BSGS) {
-    uint64_t nseq = 0x100000000ULL;  // N_SEQUENTIAL_MAX (keyhunt.cpp:464, 1272-1292)
-    if (opt.flag_n) {
-      nseq = nk_n;
-      if (nseq < 1024 || nseq % 1024) nseq = 0x100000000ULL;
+// The devices are counted once the targets are read, so the reference's lines come first.
+bool open_devices(run &R) {
+  kh_device_count(&R.ndev);
+  if (R.ndev < 1) {
+    fprintf(stderr, "[E] no GPU found\n");
+    return false;
+  }
+  R.gpus = opt.gpus > 0 ? opt.gpus : R.ndev;
+  printf("[+] GPUs : %d (%d context%s)\n", std::min(R.gpus, R.ndev), R.gpus, R.gpus == 1 ? "" : "s");
+  R.aj.resize(R.gpus);
+  R.bj.resize(R.gpus);
+  g_running = R.gpus;
+  return true;
+}
+
+// -m address / rmd160 / xpoint / vanity / minikeys: the targets (from the file, or -S's data file), the
+// mapped filter, the memory check, then one worker per context.  0 when they run, else the exit status.
+int run_address_family(run &R) {
+  std::vector<uint8_t> &rows = R.rows;
+  std::string &data_file = R.data_file;
+  uint64_t nseq = 0x100000000ULL;  // N_SEQUENTIAL_MAX (keyhunt.cpp:464, 1272-1292)
+  if (opt.flag_n) {
+    nseq = opt.n;
+    if (nseq < 1024 || nseq % 1024) nseq = 0x100000000ULL;
+  }
+  printf("[+] N = %p\n", (void *)nseq);
+  if (opt.mode == MODE_MINIKEYS) {  // keyhunt.cpp:1293-1323: the base if given, no range lines
+    if (opt.have_minikey) {
+      printf("[+] Base Minikey : %s\n", opt.minikey_str.c_str());
+    } else {  // a random base (3148-3157), drawn here instead of by the first worker
+      std::random_device rd;
+      for (int k = 0; k < 21; k++) g_mk_raw[k] = (uint8_t)((rd() & 0xFF) % 58);
     }
-    printf("[+] N = %p\n", (void *)nseq);
-    if (opt.mode == MODE_MINIKEYS) {  // keyhunt.cpp:1293-1323: the base if given, no range lines
-      if (opt.have_minikey) {
-        printf("[+] Base Minikey : %s\n", opt.minikey_str.c_str());
-      } else {  // a random base (3148-3157), drawn here instead of by the first worker
-        std::random_device rd;
-        for (int k = 0; k < 21; k++) g_mk_raw[k] = (uint8_t)((rd() & 0xFF) % 58);
-      }
-      minikey_n_init(nseq);
-    } else {
-      print_range();
-    }
-    uint64_t items = 0;
-    // -S: read the target cache if it exists (FLAGREADEDFILE1), else read the file and write it
-    bool have_data = false;
-    if (opt.save_read && opt.mode != MODE_VANITY) {
-      if (!data_file_name(opt.file, data_file)) {
-        fprintf(stderr, "[E] sha256_file error\n");
-        return EXIT_FAILURE;
-      }
-      FILE *df = fopen(data_file.c_str(), "rb");
-      if (df) {
-        fseeko(df, 0, SEEK_END);
-        const off_t size = ftello(df);
-        fclose(df);
-        have_data = true;
-        printf("[+] Reading file %s\n", data_file.c_str());
-        // a file too short for the bloom checksum or its struct bloom fails the reference's first two
-        // reads (readFileAddress, keyhunt.cpp:7068, 7076; the caller's message at 1347): e.g. the empty
-        // data file an -S --mapped-chunks N>1 run leaves behind (below)
-        if (size < 32 + 112) {  // checksum + struct bloom (112 B, kh_mapped.h struct_bloom)
-          fprintf(stderr, "[E] %s reading file, code line %d\n", size < 32 ? "Errore" : "Error", size < 32 ? 7068 : 7076);
-          fprintf(stderr, "[E] Unenexpected error\n");
-          return EXIT_FAILURE;
-        }
-      }
-    }
-    // -S with --mapped and no cache yet: the target filter is the mapped file's (bloom.dat, or the
-    // --mapped / --bloom-file name), and that filter -- its struct bloom and bits -- goes into the
-    // data file (keyhunt.cpp:7033-7049, 7630-7706, 7756-7855).  With --mapped-chunks above 1 the
-    // reference writes bloom.bytes from its FIRST chunk's mapping (bloom.bf = bf_chunks[0],
-    // bloom.cpp:395), past that mapping's end (handled below)
-    const bool mapped_data = opt.mapped && opt.save_read && opt.mode != MODE_VANITY && !have_data;
-    const bool mapped_data_chunked = mapped_data && opt.mapped_chunks > 1;
-    mapped::filter tf;
-    std::vector<uint8_t> adds;  // the items the reference adds to its (mapped) target bloom
-    std::vector<uint8_t> *addp = opt.mapped ? &adds : nullptr;
-    if (have_data) {
-      // rows and bloom come from the file, in each GPU's kh_targets_load
-    } else if (opt.mode == MODE_VANITY) {
-      if (!read_vanity(opt.file)) return EXIT_FAILURE;
-    } else if (opt.eth && opt.mode == MODE_ADDRESS) {
-      if (!read_targets_eth(opt.file, rows, items, addp)) return EXIT_FAILURE;
-    } else if (!read_targets(opt.file, opt.mode, rows, items, addp)) {
-      return EXIT_FAILURE;
-    }
-    if (opt.segwit)
-      printf("[+] Segwit targets: %llu bech32, %llu P2SH-P2WPKH\n", (unsigned long long)g_seg_bech32,
-             (unsigned long long)g_seg_p2sh);
-    if (opt.mapped) {
-      bool ok;
-      if (opt.mode == MODE_VANITY) {  // the vanity bloom: the first min_bytes bytes of every A
-        const uint32_t L = (uint32_t)opt.vanity.min_bytes;
-        for (size_t j = 0; j < opt.vanity.ranges.size(); j += 40)
-          adds.insert(adds.end(), opt.vanity.ranges.begin() + j, opt.vanity.ranges.begin() + j + L);
-        ok = mapped::targets(opt.vanity.total, adds, L);
-      } else {
-        ok = mapped::targets(items, adds, 20, mapped_data && !mapped_data_chunked ? &tf : nullptr);
-      }
-      if (!ok) return EXIT_FAILURE;
-    }
-    if (mapped_data_chunked) {
-      // The reference maps and fills the chunk files, opens data_<hex>.dat for writing, then hashes
-      // bloom.bytes from the first chunk's mapping and dies of SIGBUS past its end (writeFileIfNeeded,
-      // keyhunt.cpp:7770-7809): the chunk files hold the filter, the data file is left empty, and the next
-      // -S run fails reading it (tests/golden/ref_mapped.json "rmd160_S_mapped_chunks").  This CLI leaves
-      // the same files and exits with an error status instead of the signal.
-      FILE *f = fopen(data_file.c_str(), "wb");
-      if (f) fclose(f);
-      fflush(stdout);
-      fprintf(stderr, "[E] -S with --mapped-chunks %u: the data file would be written from the first chunk's mapping "
-                      "past its end (the reference dies of SIGBUS there); %s left empty\n",
-              (unsigned)opt.mapped_chunks, data_file.c_str());
-      return EXIT_FAILURE;
-    }
-    if (!have_data)
-      printf("[+] Sorting data ... done! %llu values were loaded and sorted\n", (unsigned long long)(rows.size() / 20));
-    if (mapped_data) {
-      printf("[D] size data %llu\n", (unsigned long long)rows.size());
-      if (!write_mapped_data_file(data_file, tf, rows)) {
-        fprintf(stderr, "[E] Error writing file %s\n", data_file.c_str());
-        return EXIT_FAILURE;
-      }
-      printf("[+] Writing file %s ........\n", data_file.c_str());
-      data_file.clear();  // the contexts take their targets from the rows
-    }
-    if (!open_devices()) return EXIT_FAILURE;
-    {
-      // contexts stacked on one device must fit its free memory (each holds its own inversion pad,
-      // kh_scan_memory): checked before any is opened, as bsgsd-amd checks its BSGS tables
-      const uint32_t smode = opt.mode == MODE_XPOINT ? KH_MODE_XPOINT
-                             : (opt.eth && (opt.mode == MODE_ADDRESS || opt.mode == MODE_RMD160)) ? KH_MODE_ETH
-                                                                                                   : KH_MODE_ADDRESS;
-      uint64_t need = 0;
-      // (-m minikeys has no walk and no pad: a queue of a few MB per context)
-      if (opt.mode != MODE_MINIKEYS &&
-          kh_scan_memory(nseq, smode | (opt.endo ? KH_MODE_ENDO : 0) | (opt.segwit && g_seg_p2sh ? KH_MODE_P2SH : 0),
-                         (uint32_t)opt.search, &need) == KH_OK) {
-        for (int dev = 0; dev < ndev && dev < gpus; dev++) {
-          const uint64_t per = (uint64_t)(gpus / ndev + (dev < gpus % ndev ? 1 : 0));
-          uint64_t fr = 0, tot = 0;
-          if (kh_device_memory(dev, &fr, &tot) == KH_OK && fr && per * need > fr) {
-            fprintf(stderr, "[E] -g %d: %llu context(s) on GPU %d need %.1f GB of device memory (%.1f GB each), "
-                            "%.1f GB are free; use fewer contexts (-g) or a smaller -n\n",
-                    gpus, (unsigned long long)per, dev, per * need / 1e9, need / 1e9, fr / 1e9);
-            return EXIT_FAILURE;
-          }
-        }
-      }
-    }
-    g_running = gpus;
-    for (int d = 0; d < gpus; d++) {
-      aj[d].device = d % ndev;
-      aj[d].index = d;
-      aj[d].rows = &rows;
-      // initBloomFilter (keyhunt.cpp:7608): max(10000, items), times -z above the floor
-      const uint64_t nitems = items ? items : rows.size() / 20;
-      aj[d].bloom_items = nitems <= 10000 ? nitems : nitems * (uint64_t)opt.bloom_mult;
-      aj[d].nseq = nseq;
-      if (!data_file.empty()) {
-        aj[d].data_file = data_file.c_str();
-        aj[d].save_data = !have_data && d == 0;  // one GPU writes the cache
-      }
-      th.emplace_back(opt.mode == MODE_MINIKEYS ? mini_worker : addr_worker, &aj[d]);
-    }
+    minikey_n_init(nseq);
   } else {
-    FILE *f = fopen(opt.file, "r");
-    if (!f) {
-      fprintf(stderr, "[E] Can't open file %s\n", opt.file);
-      return EXIT_FAILURE;
-    }
-    printf("[+] Opening file %s\n", opt.file);
-    // keyhunt.cpp:1369-1446: N = lines of 66+ characters; each such line's first token (separators
-    // " \t:") is a public key of 66 or 130 characters (ParsePublicKeyHex), else "Invalid length"
-    std::vector<std::string> lines = fgets_pieces(f, 1022);
-    fclose(f);
-    size_t counted = 0;
-    for (auto &ln : lines) counted += ln.size() >= 66;
-    if (!counted) {
-      fprintf(stderr, "[E] There is no valid data in the file\n");
-      return EXIT_FAILURE;
-    }
-    for (auto &ln : lines) {
-      if (ln.size() < 66) continue;
-      std::vector<char> buf(ln.begin(), ln.end());
-      buf.push_back(0);
-      char *tok = strtok(buf.data(), " \t:");
-      const size_t tl = tok ? strlen(tok) : 0;
-      fe x, y;
-      bool cp = false;
-      if (tl == 66 || tl == 130) {
-        const int r = parse_pubkey_hex_ref(tok, x, y, cp);
-        if (r < 0) return 255;  // the reference's exit(-1)
-        if (r > 0) {
-          tx.push_back(x);
-          ty.push_back(y);
-          comp.push_back(cp);
-        }
-      } else {
-        printf("Invalid length: %s\n", tok ? tok : "");
-      }
-    }
-    if (tx.empty()) {
-      fprintf(stderr, "[E] The file don't have any valid publickeys\n");
-      return EXIT_FAILURE;
-    }
-    printf("[+] Added %zu points from file\n", tx.size());
     print_range();
-    g_found.assign(tx.size(), 0);
-    // BSGS N: -n or 2^44 (keyhunt.cpp:1454-1471); the library validates sqrt / 1024 and derives M
-    uint64_t n = nk_n;
-    U diff = u_sub(opt.end, opt.start);
-    if (u_cmp(diff, u_from_u64(n)) < 0) {
-      fprintf(stderr, "[E] the given range is small\n");
+  }
+  uint64_t items = 0;
+  // -S: read the target cache if it exists (FLAGREADEDFILE1), else read the file and write it
+  bool have_data = false;
+  if (opt.save_read && opt.mode != MODE_VANITY) {
+    if (!data_file_name(opt.file, data_file)) {
+      fprintf(stderr, "[E] sha256_file error\n");
       return EXIT_FAILURE;
     }
-    uint64_t m = 1;
-    while ((m + 1) * (m + 1) <= n) m++;
-    uint64_t M = m * opt.kfactor;
-    uint64_t Nr = (n / M) * M;
-    twoN = u_mul_u64(u_from_u64(Nr), 2);
-    printf("[+] N = 0x%llx\n", (unsigned long long)Nr);
-    // GGSB block geometry from sqrt(N) (keyhunt.cpp:1477-1499) and the base step (1617-1627)
-    g_step = twoN;
-    uint64_t ggsb_blocks = 1, ggsb_babies = M;
-    if (opt.ggsb) {
-      uint64_t bc = opt.ggsb_count, bs = opt.ggsb_size;
-      if (bc == 0 && bs == 0) bc = 1;
-      if (bc > 0 && bs == 0)
-        bs = (m + bc - 1) / bc;
-      else if (bs > 0 && bc == 0)
-        bc = (m + bs - 1) / bs;
-      if (bc == 0) bc = 1;
-      if (bs == 0) bs = m;
-      if (bc > 1 && bs) g_step = u_mul_u64(u_from_u64(bs), 2);
-      ggsb_blocks = bc > 1 ? bc : 1;
-      if (bs) ggsb_babies = bs;
-    }
-    {
-      // keyhunt.cpp:1663-1685 (stderr): the build's layout and the expected layer / table sizes
-      const uint64_t items = M / 256 > 10000 ? M / 256 + (M % 256 ? 1 : 0) : 1000;
-      const long double err = opt.mapped && opt.mapped_error ? opt.mapped_error : 0.000001L;
-      const double shard_mb = (double)mapped::bytes_for(items, err) / 1048576.0;
-      fprintf(stderr, "[i] BSGS table build: %s layout, creating %llu block(s) of %llu babies each.\n",
-              ggsb_blocks > 1 ? "GGSB" : "classic", (unsigned long long)ggsb_blocks, (unsigned long long)ggsb_babies);
-      fprintf(stderr, "[i] Expected sizes: each bloom layer ~%.2f MB (256 shards), bPtable ~%.2f MB per block (%.2f MB total).\n",
-              shard_mb * 256.0, (double)(ggsb_babies * 16) / 1048576.0, (double)(M * 16) / 1048576.0);
-    }
-    if (opt.mapped && opt.save_read && opt.mapped_chunks > 1) {
-      // the reference writes each shard's bits from its first chunk's mapping, past that mapping's end
-      fprintf(stderr, "[E] -S with --mapped-chunks above 1: the reference writes the table files from each shard's "
-                      "first chunk mapping past its end; not provided\n");
-      return EXIT_FAILURE;
-    }
-    if (!open_devices()) return EXIT_FAILURE;
-    g_running = gpus;
-    for (int d = 0; d < gpus; d++) {
-      bj[d].device = d % ndev;
-      bj[d].first = d == 0;
-      bj[d].tx = &tx;
-      bj[d].ty = &ty;
-      bj[d].comp = &comp;
-      bj[d].n = n;
-      bj[d].k = opt.kfactor;
-      // ~2^35 giant points per engine call (16 pipelined rounds, ~1 s): the end of a call drains
-      // the pipeline (the last round's second check, the hit copies), which at 2^31 points per call
-      // cost 7 % of the rate (profiles/r03f_cli_rate_bsgs.json); a call returns as soon as every
-      // target is found.  Listed schedules take calls of the same size (at 2^31 points per call,
-      // -B random ran 17 % and -B both 9 % below sequential: profiles/r05k_cli_rate_bsgs_*.json).
-      // A range of fewer bases than that is dealt out evenly over the contexts (the reference's
-      // threads take one base each, keyhunt.cpp:4600-4617)
-      {
-        uint64_t aux = Nr / M, pts = ((aux + 1023) / 1024) * 1024;
-        bj[d].bases_per_call = std::max<uint64_t>(1, (1ULL << 35) / pts);
-        bj[d].list_bases_per_call = bj[d].bases_per_call;
-        const U span = u_sub(opt.end, opt.start);
-        if (g_step.v[1] == 0 && g_step.v[2] == 0 && g_step.v[3] == 0 && g_step.v[4] == 0) {
-          uint64_t rem = 0;
-          U nb = u_divmod_u64(span, g_step.v[0], &rem);
-          if (u_bitlen(nb) <= 40) {
-            const uint64_t bases = nb.v[0] + (rem ? 1 : 0), share = (bases + gpus - 1) / gpus;
-            bj[d].bases_per_call = std::max<uint64_t>(1, std::min(bj[d].bases_per_call, share));
-            bj[d].list_bases_per_call = std::max<uint64_t>(1, std::min(bj[d].list_bases_per_call, share));
-          }
-        }
+    FILE *df = fopen(data_file.c_str(), "rb");
+    if (df) {
+      fseeko(df, 0, SEEK_END);
+      const off_t size = ftello(df);
+      fclose(df);
+      have_data = true;
+      printf("[+] Reading file %s\n", data_file.c_str());
+      // a file too short for the bloom checksum or its struct bloom fails the reference's first two
+      // reads (readFileAddress, keyhunt.cpp:7068, 7076; the caller's message at 1347): e.g. the empty
+      // data file an -S --mapped-chunks N>1 run leaves behind (below)
+      if (size < 32 + 112) {  // checksum + struct bloom (112 B, kh_mapped.h struct_bloom)
+        fprintf(stderr, "[E] %s reading file, code line %d\n", size < 32 ? "Errore" : "Error", size < 32 ? 7068 : 7076);
+        fprintf(stderr, "[E] Unenexpected error\n");
+        return EXIT_FAILURE;
       }
-      th.emplace_back(bsgs_worker, &bj[d]);
     }
   }
-  // stats loop (keyhunt.cpp:2850-2962)
+  // -S with --mapped and no cache yet: the target filter is the mapped file's (bloom.dat, or the
+  // --mapped / --bloom-file name), and that filter -- its struct bloom and bits -- goes into the
+  // data file (keyhunt.cpp:7033-7049, 7630-7706, 7756-7855).  With --mapped-chunks above 1 the
+  // reference writes bloom.bytes from its FIRST chunk's mapping (bloom.bf = bf_chunks[0],
+  // bloom.cpp:395), past that mapping's end (handled below)
+  const bool mapped_data = opt.mapped && opt.save_read && opt.mode != MODE_VANITY && !have_data;
+  const bool mapped_data_chunked = mapped_data && mapped::cfg.chunks > 1;
+  mapped::filter tf;
+  std::vector<uint8_t> adds;  // the items the reference adds to its (mapped) target bloom
+  std::vector<uint8_t> *addp = opt.mapped ? &adds : nullptr;
+  if (have_data) {
+    // rows and bloom come from the file, in each GPU's kh_targets_load
+  } else if (opt.mode == MODE_VANITY) {
+    if (!read_vanity(opt.file)) return EXIT_FAILURE;
+  } else if (opt.eth && opt.mode == MODE_ADDRESS) {
+    if (!read_targets_eth(opt.file, rows, items, addp)) return EXIT_FAILURE;
+  } else if (!read_targets(opt.file, opt.mode, rows, items, addp)) {
+    return EXIT_FAILURE;
+  }
+  if (opt.segwit)
+    printf("[+] Segwit targets: %llu bech32, %llu P2SH-P2WPKH\n", (unsigned long long)g_seg_bech32,
+           (unsigned long long)g_seg_p2sh);
+  if (opt.mapped) {
+    bool ok;
+    if (opt.mode == MODE_VANITY) {  // the vanity bloom: the first min_bytes bytes of every A
+      const uint32_t L = (uint32_t)opt.vanity.min_bytes;
+      for (size_t j = 0; j < opt.vanity.ranges.size(); j += 40)
+        adds.insert(adds.end(), opt.vanity.ranges.begin() + j, opt.vanity.ranges.begin() + j + L);
+      ok = mapped::targets(opt.vanity.total, adds, L);
+    } else {
+      ok = mapped::targets(items, adds, 20, mapped_data && !mapped_data_chunked ? &tf : nullptr);
+    }
+    if (!ok) return EXIT_FAILURE;
+  }
+  if (mapped_data_chunked) {
+    // The reference maps and fills the chunk files, opens data_<hex>.dat for writing, then hashes
+    // bloom.bytes from the first chunk's mapping and dies of SIGBUS past its end (writeFileIfNeeded,
+    // keyhunt.cpp:7770-7809): the chunk files hold the filter, the data file is left empty, and the next
+    // -S run fails reading it (tests/golden/ref_mapped.json "rmd160_S_mapped_chunks").  This CLI leaves
+    // the same files and exits with an error status instead of the signal.
+    FILE *f = fopen(data_file.c_str(), "wb");
+    if (f) fclose(f);
+    fflush(stdout);
+    fprintf(stderr, "[E] -S with --mapped-chunks %u: the data file would be written from the first chunk's mapping "
+                    "past its end (the reference dies of SIGBUS there); %s left empty\n",
+            (unsigned)mapped::cfg.chunks, data_file.c_str());
+    return EXIT_FAILURE;
+  }
+  if (!have_data)
+    printf("[+] Sorting data ... done! %llu values were loaded and sorted\n", (unsigned long long)(rows.size() / 20));
+  if (mapped_data) {
+    printf("[D] size data %llu\n", (unsigned long long)rows.size());
+    if (!write_mapped_data_file(data_file, tf, rows)) {
+      fprintf(stderr, "[E] Error writing file %s\n", data_file.c_str());
+      return EXIT_FAILURE;
+    }
+    printf("[+] Writing file %s ........\n", data_file.c_str());
+    data_file.clear();  // the contexts take their targets from the rows
+  }
+  if (!open_devices(R)) return EXIT_FAILURE;
+  // contexts stacked on one device must fit its free memory (each holds its own inversion pad,
+  // kh_scan_memory): checked before any is opened, as bsgsd-amd checks its BSGS tables
+  // (-m minikeys has no walk and no pad: a queue of a few MB per context)
+  const uint32_t mode = scan_mode();
+  uint64_t need = 0;
+  if (opt.mode != MODE_MINIKEYS && kh_scan_memory(nseq, mode, (uint32_t)opt.search, &need) == KH_OK) {
+    std::vector<uint64_t> dev_free(R.ndev, 0);
+    for (int dev = 0; dev < R.ndev && dev < R.gpus; dev++)
+      if (kh_device_memory(dev, &dev_free[dev], nullptr) != KH_OK) dev_free[dev] = 0;
+    if (!contexts_fit(R.gpus, R.ndev, need, dev_free, "-n")) return EXIT_FAILURE;
+  }
+  for (int d = 0; d < R.gpus; d++) {
+    addr_job &j = R.aj[d];
+    j.device = d % R.ndev;
+    j.index = d;
+    j.rows = &rows;
+    // initBloomFilter (keyhunt.cpp:7608): max(10000, items), times -z above the floor
+    const uint64_t nitems = items ? items : rows.size() / 20;
+    j.bloom_items = nitems <= 10000 ? nitems : nitems * (uint64_t)opt.bloom_mult;
+    j.nseq = nseq;
+    j.mode = mode;
+    if (!data_file.empty()) {
+      j.data_file = data_file.c_str();
+      j.save_data = !have_data && d == 0;  // one GPU writes the cache
+    }
+    R.th.emplace_back(opt.mode == MODE_MINIKEYS ? mini_worker : addr_worker, &j);
+  }
+  return 0;
+}
+
+// keyhunt.cpp:1369-1446: N = lines of 66+ characters; each such line's first token (separators
+// " \t:") is a public key of 66 or 130 characters (ParsePublicKeyHex), else "Invalid length".
+// 0, or the exit status.
+int read_bsgs_targets(run &R) {
+  FILE *f = fopen(opt.file, "r");
+  if (!f) {
+    fprintf(stderr, "[E] Can't open file %s\n", opt.file);
+    return EXIT_FAILURE;
+  }
+  printf("[+] Opening file %s\n", opt.file);
+  std::vector<std::string> lines = fgets_pieces(f, 1022);
+  fclose(f);
+  size_t counted = 0;
+  for (auto &ln : lines) counted += ln.size() >= 66;
+  if (!counted) {
+    fprintf(stderr, "[E] There is no valid data in the file\n");
+    return EXIT_FAILURE;
+  }
+  for (auto &ln : lines) {
+    if (ln.size() < 66) continue;
+    std::vector<char> buf(ln.begin(), ln.end());
+    buf.push_back(0);
+    char *tok = strtok(buf.data(), " \t:");
+    const size_t tl = tok ? strlen(tok) : 0;
+    fe x, y;
+    bool cp = false;
+    if (tl == 66 || tl == 130) {
+      const int r = parse_pubkey_hex_ref(tok, x, y, cp);
+      if (r < 0) return 255;  // the reference's exit(-1)
+      if (r > 0) {
+        R.tx.push_back(x);
+        R.ty.push_back(y);
+        R.comp.push_back(cp);
+      }
+    } else {
+      printf("Invalid length: %s\n", tok ? tok : "");
+    }
+  }
+  if (R.tx.empty()) {
+    fprintf(stderr, "[E] The file don't have any valid publickeys\n");
+    return EXIT_FAILURE;
+  }
+  printf("[+] Added %zu points from file\n", R.tx.size());
+  return 0;
+}
+
+// -m bsgs: the targets, N and the GGSB geometry with their lines, then one worker per context.
+// 0 when they run, else the exit status.
+int run_bsgs(run &R) {
+  if (int rc = read_bsgs_targets(R)) return rc;
+  print_range();
+  g_found.assign(R.tx.size(), 0);
+  // BSGS N: -n or 2^44 (keyhunt.cpp:1454-1471); the library validates sqrt / 1024 and derives M
+  const uint64_t n = opt.n;
+  if (u_cmp(u_sub(opt.end, opt.start), u_from_u64(n)) < 0) {
+    fprintf(stderr, "[E] the given range is small\n");
+    return EXIT_FAILURE;
+  }
+  uint64_t m = 1;
+  while ((m + 1) * (m + 1) <= n) m++;
+  const uint64_t M = m * opt.kfactor, Nr = (n / M) * M;
+  R.twoN = u_mul_u64(u_from_u64(Nr), 2);
+  printf("[+] N = 0x%llx\n", (unsigned long long)Nr);
+  // GGSB block geometry from sqrt(N) (keyhunt.cpp:1477-1499) and the base step (1617-1627)
+  g_step = R.twoN;
+  uint64_t ggsb_blocks = 1, ggsb_babies = M;
+  if (opt.ggsb) {
+    uint64_t bc = opt.ggsb_count, bs = opt.ggsb_size;
+    if (bc == 0 && bs == 0) bc = 1;
+    if (bc > 0 && bs == 0)
+      bs = (m + bc - 1) / bc;
+    else if (bs > 0 && bc == 0)
+      bc = (m + bs - 1) / bs;
+    if (bc == 0) bc = 1;
+    if (bs == 0) bs = m;
+    if (bc > 1 && bs) g_step = u_mul_u64(u_from_u64(bs), 2);
+    ggsb_blocks = bc > 1 ? bc : 1;
+    if (bs) ggsb_babies = bs;
+  }
+  {
+    // keyhunt.cpp:1663-1685 (stderr): the build's layout and the expected layer / table sizes
+    const uint64_t items = M / 256 > 10000 ? M / 256 + (M % 256 ? 1 : 0) : 1000;
+    const long double err = opt.mapped && mapped::cfg.error ? mapped::cfg.error : 0.000001L;
+    const double shard_mb = (double)mapped::bytes_for(items, err) / 1048576.0;
+    fprintf(stderr, "[i] BSGS table build: %s layout, creating %llu block(s) of %llu babies each.\n",
+            ggsb_blocks > 1 ? "GGSB" : "classic", (unsigned long long)ggsb_blocks, (unsigned long long)ggsb_babies);
+    fprintf(stderr, "[i] Expected sizes: each bloom layer ~%.2f MB (256 shards), bPtable ~%.2f MB per block (%.2f MB total).\n",
+            shard_mb * 256.0, (double)(ggsb_babies * 16) / 1048576.0, (double)(M * 16) / 1048576.0);
+  }
+  if (opt.mapped && opt.save_read && mapped::cfg.chunks > 1) {
+    // the reference writes each shard's bits from its first chunk's mapping, past that mapping's end
+    fprintf(stderr, "[E] -S with --mapped-chunks above 1: the reference writes the table files from each shard's "
+                    "first chunk mapping past its end; not provided\n");
+    return EXIT_FAILURE;
+  }
+  if (!open_devices(R)) return EXIT_FAILURE;
+  // ~2^35 giant points per engine call (16 pipelined rounds, ~1 s): the end of a call drains
+  // the pipeline (the last round's second check, the hit copies), which at 2^31 points per call
+  // cost 7 % of the rate (profiles/r03f_cli_rate_bsgs.json); a call returns as soon as every
+  // target is found.  Listed schedules take calls of the same size (at 2^31 points per call,
+  // -B random ran 17 % and -B both 9 % below sequential: profiles/r05k_cli_rate_bsgs_*.json).
+  // A range of fewer bases than that is dealt out evenly over the contexts (the reference's
+  // threads take one base each, keyhunt.cpp:4600-4617)
+  const uint64_t aux = Nr / M, pts = ((aux + 1023) / 1024) * 1024;
+  uint64_t per_call = std::max<uint64_t>(1, (1ULL << 35) / pts);
+  if (g_step.v[1] == 0 && g_step.v[2] == 0 && g_step.v[3] == 0 && g_step.v[4] == 0) {
+    uint64_t rem = 0;
+    const U nb = u_divmod_u64(u_sub(opt.end, opt.start), g_step.v[0], &rem);
+    if (u_bitlen(nb) <= 40) {
+      const uint64_t bases = nb.v[0] + (rem ? 1 : 0), share = (bases + R.gpus - 1) / R.gpus;
+      per_call = std::max<uint64_t>(1, std::min(per_call, share));
+    }
+  }
+  for (int d = 0; d < R.gpus; d++) {
+    bsgs_job &j = R.bj[d];
+    j.device = d % R.ndev;
+    j.first = d == 0;
+    j.tx = &R.tx;
+    j.ty = &R.ty;
+    j.comp = &R.comp;
+    j.n = n;
+    j.k = opt.kfactor;
+    j.bases_per_call = j.list_bases_per_call = per_call;
+    R.th.emplace_back(bsgs_worker, &j);
+  }
+  return 0;
+}
+
+// the stats loop (keyhunt.cpp:2850-2962) until every worker has ended; the program's exit status
+int wait_for_workers(run &R) {
   uint64_t secs = 0;
   while (g_running > 0) {
     sleep(1);
     secs++;
-    if (opt.seconds > 0 && secs % opt.seconds == 0) print_stats(secs, keys_done(twoN));
+    if (opt.seconds > 0 && secs % opt.seconds == 0) print_stats(secs, keys_done(R.twoN));
   }
-  for (auto &t : th) t.join();
+  for (auto &t : R.th) t.join();
   int rc = 0;
-  for (int d = 0; d < gpus; d++) rc |= (opt.mode == MODE_BSGS ? bj[d].rc : aj[d].rc);
+  for (int d = 0; d < R.gpus; d++) rc |= (opt.mode == MODE_BSGS ? R.bj[d].rc : R.aj[d].rc);
   printf("\nEnd\n");
   return rc ? EXIT_FAILURE : EXIT_SUCCESS;
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+  printf("[+] Version %s\n", VERSION);
+  int status = EXIT_FAILURE;
+  if (!parse_options(argc, argv, status)) return status;
+  if (!check_options()) return EXIT_FAILURE;
+  setup_range();
+  run R;
+  if (int rc = opt.mode == MODE_BSGS ? run_bsgs(R) : run_address_family(R)) return rc;
+  return wait_for_workers(R);
 }

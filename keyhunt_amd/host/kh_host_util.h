@@ -1,10 +1,13 @@
 // kh_host_util.h -- host helpers shared by the engine's command-line programs (keyhunt-amd,
 // bsgsd-amd): 256-bit range arithmetic and hex I/O (the reference's Int, secp256k1/Int.cpp),
-// public-key parsing (Secp256K1::ParsePublicKeyHex, secp256k1/SECP256K1.cpp:327-380) and the
-// -n/-k validation (util.c:358-389).
+// public-key parsing (Secp256K1::ParsePublicKeyHex, secp256k1/SECP256K1.cpp:327-380), the text of a
+// hit (public key, base58check address), size and -n arguments, the -n/-k validation
+// (util.c:358-389), the -g memory check and MD5.  No GPU calls.
 #pragma once
+#include <ctype.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -206,6 +209,24 @@ inline void trim(char *s) {
   if (i) memmove(s, s + i, n - i + 1);
 }
 
+// a size argument (--ptable-size, --mapped-size; keyhunt.cpp:749-765, 774-785, bsgsd.cpp:804-841): decimal,
+// times 1024 per step of a k/m/g/t suffix in either case; any other suffix is ignored
+inline uint64_t parse_size(const char *s) {
+  char *end;
+  uint64_t v = strtoull(s, &end, 10);
+  switch (tolower(*end)) {
+    case 't': v *= 1024ull; [[fallthrough]];
+    case 'g': v *= 1024ull; [[fallthrough]];
+    case 'm': v *= 1024ull; [[fallthrough]];
+    case 'k': v *= 1024ull;
+  }
+  return v;
+}
+// -n: decimal, or hex after 0x / 0X
+inline uint64_t parse_n(const char *s) {
+  return (s[0] == '0' && (s[1] == 'x' || s[1] == 'X')) ? strtoull(s + 2, nullptr, 16) : strtoull(s, nullptr, 10);
+}
+
 inline bool parse_pubkey(const char *s, fe &x, fe &y, bool &compressed) {
   size_t n = strlen(s);
   uint8_t raw[65];
@@ -305,13 +326,96 @@ inline int parse_pubkey_hex_ref(const char *s, fe &x, fe &y, bool &compressed) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// hashing / encoding for hit output
+// ---------------------------------------------------------------------------------------------
+inline void sha256(const uint8_t *msg, size_t len, uint8_t out[32]) {
+  uint32_t st[8];
+  sha256_init(st);
+  size_t off = 0;
+  uint32_t w[16];
+  auto load = [&](const uint8_t *b) {
+    for (int i = 0; i < 16; i++)
+      w[i] = ((uint32_t)b[4 * i] << 24) | ((uint32_t)b[4 * i + 1] << 16) | ((uint32_t)b[4 * i + 2] << 8) | b[4 * i + 3];
+  };
+  while (len - off >= 64) {
+    load(msg + off);
+    sha256_transform(st, w);
+    off += 64;
+  }
+  uint8_t blk[128] = {0};
+  size_t rem = len - off;
+  memcpy(blk, msg + off, rem);
+  blk[rem] = 0x80;
+  size_t nb = rem >= 56 ? 2 : 1;
+  uint64_t bits = (uint64_t)len * 8;
+  for (int i = 0; i < 8; i++) blk[nb * 64 - 1 - i] = (uint8_t)(bits >> (8 * i));
+  for (size_t b = 0; b < nb; b++) {
+    load(blk + 64 * b);
+    sha256_transform(st, w);
+  }
+  for (int i = 0; i < 8; i++) {
+    out[4 * i] = st[i] >> 24;
+    out[4 * i + 1] = st[i] >> 16;
+    out[4 * i + 2] = st[i] >> 8;
+    out[4 * i + 3] = st[i];
+  }
+}
+inline const char *B58 = "123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz";
+inline std::string b58enc(const uint8_t *d, int n) {
+  std::vector<uint8_t> buf;
+  int zeros = 0;
+  while (zeros < n && d[zeros] == 0) zeros++;
+  for (int i = zeros; i < n; i++) {
+    int carry = d[i];
+    for (auto &b : buf) {
+      carry += b * 256;
+      b = carry % 58;
+      carry /= 58;
+    }
+    while (carry) {
+      buf.push_back(carry % 58);
+      carry /= 58;
+    }
+  }
+  std::string s(zeros, '1');
+  for (auto it = buf.rbegin(); it != buf.rend(); ++it) s += B58[*it];
+  return s;
+}
+inline std::string rmd_to_address(const uint8_t h[20], uint8_t version = 0) {
+  uint8_t d[25], c1[32], c2[32];
+  d[0] = version;
+  memcpy(d + 1, h, 20);
+  sha256(d, 21, c1);
+  sha256(c1, 32, c2);
+  memcpy(d + 21, c2, 4);
+  return b58enc(d, 25);
+}
+// a hit's public key (X ‖ Y, big-endian, as kh_pubkeys gives it) as the hit records print it, 02/03 ‖ X or
+// 04 ‖ X ‖ Y in hex, and the hash160 of that form
+inline std::string pubkey_text(const uint8_t xy[64], bool compressed) {
+  const uint8_t pfx = compressed ? 2 + (xy[63] & 1) : 4;
+  return hex(&pfx, 1) + hex(xy, compressed ? 32 : 64);
+}
+inline void pubkey_hash160(const uint8_t xy[64], bool compressed, uint8_t rmd[20]) {
+  fe x, y;
+  fe_from_be(x, xy);
+  fe_from_be(y, xy + 32);
+  uint32_t hw[5];
+  if (compressed)
+    hash160_comp(x, 2 + (xy[63] & 1), hw);
+  else
+    hash160_uncomp(x, y, hw);
+  memcpy(rmd, hw, 20);
+}
+
+// ---------------------------------------------------------------------------------------------
 // vanity targets
 // ---------------------------------------------------------------------------------------------
 // b58tobin (base58/base58.c, libbase58): big-endian into *binszp bytes with 32-bit limbs, false on
 // an invalid digit or overflow (then *binszp is unchanged); else *binszp = the canonical length
 // (binsz - leading zero bytes + leading '1's)
 inline bool b58tobin_ref(uint8_t *bin, size_t *binszp, const char *b58, size_t b58sz) {
-  static const char *D = "123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz";
+  const char *D = B58;
   const size_t binsz = *binszp;
   const size_t outisz = (binsz + 3) / 4;
   std::vector<uint32_t> outi(outisz ? outisz : 1, 0);
@@ -349,7 +453,7 @@ inline bool b58tobin_ref(uint8_t *bin, size_t *binszp, const char *b58, size_t b
 
 inline bool is_base58(const char *s) {
   for (; *s; s++)
-    if (!strchr("123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz", *s)) return false;
+    if (!strchr(B58, *s)) return false;
   return true;
 }
 
@@ -496,6 +600,21 @@ inline bool validate_nk(uint64_t n, uint64_t k) {
   return true;
 }
 
+// -g: `gpus` contexts on devices d % ndev, each needing `need` bytes, must fit what every device has
+// free (free[dev], 0 where it could not be measured); `hint` names the options that make a context smaller
+inline bool contexts_fit(int gpus, int ndev, uint64_t need, const std::vector<uint64_t> &free, const char *hint) {
+  for (int dev = 0; dev < ndev && dev < gpus; dev++) {
+    const uint64_t per = (uint64_t)(gpus / ndev + (dev < gpus % ndev ? 1 : 0));
+    if (free[dev] && per * need > free[dev]) {
+      fprintf(stderr, "[E] -g %d: %llu context(s) on GPU %d need %.1f GB of device memory (%.1f GB each), "
+                      "%.1f GB are free; use fewer contexts (-g) or a smaller %s\n",
+              gpus, (unsigned long long)per, dev, per * need / 1e9, need / 1e9, free[dev] / 1e9, hint);
+      return false;
+    }
+  }
+  return true;
+}
+
 // MD5 (RFC 1321) of a file, for --ptable-cache's FILE.md5 and FILE.cache (keyhunt.cpp:1958-1981,
 // 2655-2700).
 struct md5_ctx {
@@ -574,67 +693,6 @@ inline bool md5_of_file(const char *path, uint8_t out[16]) {
   const bool ok = !ferror(f);
   fclose(f);
   if (ok) c.final(out);
-  return ok;
-}
-
-// FILE.md5 as keyhunt writes and reads it: the hex MD5 and a newline (keyhunt.cpp:186-241)
-inline bool read_md5_file(const char *path, uint8_t out[16]) {
-  char buf[64] = {0};
-  FILE *f = fopen(path, "r");
-  if (!f) return false;
-  size_t n = fread(buf, 1, sizeof buf - 1, f);
-  fclose(f);
-  buf[n] = 0;
-  if (char *nl = strchr(buf, '\n')) *nl = 0;
-  if (strlen(buf) < 32) return false;
-  buf[32] = 0;
-  return hex2bin(buf, out, 16);
-}
-inline bool write_md5_file(const char *path, const uint8_t md5[16]) {
-  FILE *f = fopen(path, "w");
-  bool ok = f && fprintf(f, "%s\n", hex(md5, 16).c_str()) > 0;
-  if (f) ok = fclose(f) == 0 && ok;
-  return ok;
-}
-
-// FILE.cache: struct bptable_cache_file {magic 'BPTC', version 1, entries, md5, 257 bucket starts by
-// value[0] of the 16-byte rows} (keyhunt.cpp:137-143, 186-241; bsgsd.cpp:255-360)
-#pragma pack(push, 1)
-struct bptable_cache_file {
-  uint32_t magic, version;
-  uint64_t entries;
-  uint8_t md5[16];
-  uint64_t boundaries[257];
-};
-#pragma pack(pop)
-static_assert(sizeof(bptable_cache_file) == 2088, "struct bptable_cache_file");
-// 1: a cache of this MD5 and row count, -1: another one, 0: none readable
-inline int bptable_cache_status(const char *path, const uint8_t md5[16], uint64_t m3) {
-  bptable_cache_file disk;
-  FILE *f = fopen(path, "rb");
-  if (!f) return 0;
-  int st = 0;
-  if (fread(&disk, sizeof disk, 1, f) == 1)
-    st = disk.magic == 0x42505443u && disk.version == 1 && disk.entries == m3 && !memcmp(disk.md5, md5, 16) ? 1 : -1;
-  fclose(f);
-  return st;
-}
-inline bool bptable_cache_write(const char *path, const uint8_t md5[16], const uint8_t *rows, uint64_t m3) {
-  bptable_cache_file fc;
-  memset(&fc, 0, sizeof fc);
-  fc.magic = 0x42505443u;
-  fc.version = 1;
-  fc.entries = m3;
-  memcpy(fc.md5, md5, 16);
-  uint64_t pos = 0;
-  for (int bucket = 0; bucket < 256; bucket++) {
-    while (pos < m3 && rows[pos * 16] < bucket) pos++;
-    fc.boundaries[bucket] = pos;
-  }
-  fc.boundaries[256] = m3;
-  FILE *f = fopen(path, "wb");
-  bool ok = f && fwrite(&fc, sizeof fc, 1, f) == 1;
-  if (f) ok = fclose(f) == 0 && ok;
   return ok;
 }
 

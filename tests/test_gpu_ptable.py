@@ -13,6 +13,7 @@ import subprocess
 
 import pytest
 
+from _bptable import cache_model as _cache_model
 from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
@@ -114,19 +115,6 @@ def test_ptable_equals_reference_cli_file(work):
     shutil.copy(ref_dir / "bp.tbl", work / "ref.tbl")
     p, keys = _run(work, ["--ptable", "ref.tbl", "--load-ptable"])
     assert keys == [f"{KEY63:x}"]
-
-
-def _cache_model(rows: bytes) -> bytes:
-    """struct bptable_cache_file (keyhunt.cpp:137-143) as build_bptable_cache fills it (186-197)."""
-    import struct
-    m3 = len(rows) // 16
-    b, pos = [], 0
-    for bucket in range(256):
-        while pos < m3 and rows[pos * 16] < bucket:
-            pos += 1
-        b.append(pos)
-    b.append(m3)
-    return struct.pack("<IIQ16s257Q", 0x42505443, 1, m3, hashlib.md5(rows).digest(), *b)
 
 
 def test_ptable_cache_files(work):
