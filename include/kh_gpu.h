@@ -10,6 +10,7 @@
  *   kh_set_targets     <- readFileAddress/forceReadFileAddress/...XPoint  keyhunt.cpp:7239-7490
  *                         + initBloomFilter 7605-7626 + _sort 1359-1364
  *   kh_minikeys_scan   <- thread_process_minikeys, one chunk of N valid minikeys  keyhunt.cpp:3184-3255
+ *   kh_taproot_scan    <- nothing: the reference has no taproot search (its TODO lists bech32 addresses)
  *   kh_bsgs_setup      <- BSGS parameter block                            keyhunt.cpp:1454-1842
  *   kh_bsgs_build      <- thread_bPload / thread_bPload_2blooms + bsgs_sort keyhunt.cpp:5284-5644, 2466-2503
  *   kh_bsgs_scan       <- thread_process_bsgs (sequential), bases of 2N   keyhunt.cpp:4549-4888
@@ -76,6 +77,7 @@ extern "C" {
 #define KH_KIND_04 2       /* hash160(04||X||Y) matched */
 #define KH_KIND_XPOINT 3   /* X[0..20) matched */
 #define KH_KIND_ETH 5      /* Ethereum address matched (key printed by writekeyeth) */
+#define KH_KIND_TAPROOT 6  /* kh_taproot_scan: the taproot output key of the point matched a witness program */
 /* with KH_MODE_ENDO, kind also carries the image and (for 04 hashes) the Y sign: */
 #define KH_KIND_ENDO1 0x10 /* matched on (beta*X, Y): key = lambda*k (+- as reported) */
 #define KH_KIND_ENDO2 0x20 /* matched on (beta^2*X, Y): key = lambda^2*k */
@@ -213,6 +215,37 @@ int kh_minikeys_valid(kh_ctx *ctx, const uint8_t base[21], uint64_t n_candidates
 int kh_minikeys_keys(kh_ctx *ctx, const uint8_t base[21], const uint64_t *offsets, uint32_t n, uint8_t *out52);
 int kh_minikeys_queue(kh_ctx *ctx, uint32_t *entries, uint32_t *redos);
 
+/* ---- taproot ------------------------------------------------------------------------------ */
+/* P2TR key-path targets (bc1p... addresses, BIP-341 / BIP-86).  The witness program of such an address is
+ * no key hash: it is the x-coordinate of the tweaked key Q = lift_x(P.x) + t*G, t = SHA-256(tag || tag ||
+ * P.x) read big-endian with tag = SHA-256("TapTweak"), P = k*G the internal key.  Only outputs without a
+ * script tree (key-path-only, what BIP-86 wallets hand out) can be found: with a script tree the tweak
+ * also covers the tree's root, which no key search knows.
+ * kh_taproot_set_targets: n 32-byte witness programs, any order.  They are kept beside the rows of
+ * kh_set_targets / kh_targets_load, which they do not replace: one context can hold both and serve
+ * kh_scan and kh_taproot_scan in turn.  n = 0 drops them. */
+int kh_taproot_set_targets(kh_ctx *ctx, const uint8_t *progs32, uint64_t n);
+/* Keys start + i*stride, i in [0, n_keys) (n_keys a multiple of 1024; stride NULL -> 1), in windows of
+ * kh_taproot_set_window points: the lanes are set up and walked with X and Y kept on the device, and the
+ * tweak kernel (k_tap_keys) computes every point's output key and probes a blocked filter of the programs'
+ * first 20 bytes; the host confirms each filter hit on all 32 bytes.  hits, in offset order: key = the
+ * BIP-340 secret key of the internal key (k if P.y is even, else n - k: what a tr(KEY) descriptor takes),
+ * offset = i, kind = KH_KIND_TAPROOT, compressed = 1.  More hits than cap: KH_E_OVERFLOW with *n_hits the
+ * true count.  KH_E_ARG: null pointers, start or stride 0, n_keys 0 or no multiple of 1024; KH_E_STATE: no
+ * programs set; KH_E_RANGE, before any launch: start + n_keys*stride reaches the group order.  The call
+ * moves the context's lanes: a following kh_scan or kh_bsgs_scan starts its lanes afresh. */
+int kh_taproot_scan(kh_ctx *ctx, const uint8_t start[32], const uint8_t stride[32], uint64_t n_keys, kh_hit *hits,
+                    uint32_t cap, uint32_t *n_hits);
+/* points per window: a multiple of 1024, at most 2^24; 0 = the default, 2^24 (1 GB of X and Y on the device) */
+int kh_taproot_set_window(kh_ctx *ctx, uint64_t points);
+/* parity hook: the tweak kernel on n given points {x[32], y[32]} (big-endian; at most 2^24) with no filter ->
+ * per point the 32-byte output key, or 32 zero bytes where BIP-341 fails (t >= n).  The points are taken as
+ * given: Y decides the sign of P', the curve equation is not checked. */
+int kh_taproot_outputs(kh_ctx *ctx, const uint8_t *xy, uint32_t n, uint8_t *out32);
+/* the tweak kernel's compiled batch (points per lane that share one inversion), and the filter hits the
+ * device reported in the last kh_taproot_scan, before the host's confirmation */
+int kh_taproot_stats(kh_ctx *ctx, uint32_t *batch, uint32_t *device_hits);
+
 /* ---- BSGS --------------------------------------------------------------------------------- */
 /* layer-1 layout for the next kh_bsgs_setup (KH_LAYER1_BLOCKED unless changed) */
 int kh_bsgs_set_layer1(kh_ctx *ctx, uint32_t layout);
@@ -273,7 +306,7 @@ int kh_bsgs_refine_stats(kh_ctx *ctx, uint64_t *first_level, uint64_t *second_le
 /* Accumulated device time of walk launches of one kind since the last reset, measured with
  * HIP events on the context's stream.  kind: 0 address/rmd160, 1 xpoint, 2 bsgs giant,
  * 3 bsgs build, 4 lane setup (scalar mult), 5 minikeys filter (points = candidates), 6 minikeys keys
- * (points = valid candidates). */
+ * (points = valid candidates), 7 taproot tweak kernel (kh_taproot_scan's walks count under 0 and 4). */
 int kh_kernel_time(kh_ctx *ctx, uint32_t kind, uint64_t *launches, double *ms, uint64_t *points);
 int kh_kernel_time_reset(kh_ctx *ctx);
 

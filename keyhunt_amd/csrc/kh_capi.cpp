@@ -1,6 +1,6 @@
 // kh_capi.cpp -- implementation of include/kh_gpu.h: the context, the shared launch helpers, targets,
-// kh_scan and the target files.  (BSGS: kh_capi_bsgs.cpp; minikeys: kh_capi_minikeys.cpp; parity
-// hooks and timing: kh_capi_hooks.cpp.)
+// kh_scan and the target files.  (BSGS: kh_capi_bsgs.cpp; minikeys: kh_capi_minikeys.cpp; taproot
+// targets: kh_capi_taproot.cpp; parity hooks and timing: kh_capi_hooks.cpp.)
 //
 // Host side of the MI355X engine: device memory layout, lane partitioning, launches, the
 // reference-exact host steps around the kernels (bloom sizing, table sort + searchbinary,

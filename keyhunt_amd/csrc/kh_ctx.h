@@ -1,6 +1,6 @@
 // kh_ctx.h -- the context behind include/kh_gpu.h and the helpers its translation units share:
-// kh_capi.cpp (open/close, targets, kh_scan, target files), kh_capi_bsgs.cpp, kh_capi_minikeys.cpp
-// and kh_capi_hooks.cpp.
+// kh_capi.cpp (open/close, targets, kh_scan, target files), kh_capi_bsgs.cpp, kh_capi_minikeys.cpp,
+// kh_capi_taproot.cpp and kh_capi_hooks.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
@@ -145,9 +145,20 @@ struct kh_ctx {
   dev_buf<uint64_t> d_mkq;
   dev_buf<uint32_t> d_mk_count;
 
+  // taproot (kh_capi_taproot.cpp): the sorted 32-byte witness programs, the blocked filter of their first
+  // 20 bytes (its own, beside d_tblk), the points per window (0 = the default), the window's X and Y in
+  // the KM_DUMP layout, and the filter hits the device reported in the last kh_taproot_scan
+  std::vector<uint8_t> tap_progs;
+  uint64_t n_tap = 0;
+  dev_buf<uint4> d_tap_blk;
+  uint32_t tap_blocks = 0;
+  uint64_t tap_window = 0;
+  dev_buf<uint32_t> d_tap_x, d_tap_y;
+  uint32_t tap_dev_hits = 0;
+
   // timing
   gpu_event ev_a, ev_b;
-  timing tm[7];  // kh_kernel_time kinds 0..6
+  timing tm[8];  // kh_kernel_time kinds 0..7
 
   // pipelined BSGS rounds: double-buffered hit buffers, pinned host mirrors, host scalar arrays
   dev_buf<uint32_t> d_cnt2[2];

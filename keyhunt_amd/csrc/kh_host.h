@@ -256,6 +256,45 @@ struct comb_table {
   }
 };
 
+// the process's own comb table, built on first use (hosts without a context: the CLI's hit text, tests)
+inline const comb_table &host_comb() {
+  static const comb_table c = [] {
+    comb_table t;
+    t.build();
+    return t;
+  }();
+  return c;
+}
+
+// BIP-341 key-path output key of the internal key P = (x, y) (no script tree, BIP-86): out32 = x(Q),
+// Q = P' + t*G with P' = P of even Y (lift_x(x); y spares the square root) and t = SHA-256_TapTweak(x)
+// read big-endian.  false where BIP-341 fails: t >= n, or Q the point at infinity (t*G = -P').  The twin
+// of k_tap_keys on the host comb: the scan's hit confirmation and the CLI's hit text use it.
+inline bool taproot_output_x(const comb_table &comb, const fe &x, const fe &y, uint8_t out32[32]) {
+  uint32_t st[8];
+  taptweak_hash(x, st);
+  u256 t;
+  for (int i = 0; i < 4; i++) t.v[i] = ((uint64_t)st[6 - 2 * i] << 32) | st[7 - 2 * i];
+  if (u256_cmp(t, ORDER_N) >= 0) return false;
+  ge p{x, y};
+  if (y.d[0] & 1u) fe_neg(p.y, y);
+  ge q = p;
+  ge tg;
+  if (comb.mult(tg, t)) {
+    if (fe_eq(tg.x, p.x)) {
+      if (!fe_eq(tg.y, p.y)) return false;
+      ge_double(q, p);
+    } else {
+      ge_add(q, tg, p);
+    }
+  }
+  fe_to_be(out32, q.x);
+  return true;
+}
+inline bool taproot_output_x(const fe &x, const fe &y, uint8_t out32[32]) {
+  return taproot_output_x(host_comb(), x, y, out32);
+}
+
 // Montgomery-trick batch inversion (IntGroup::ModInv); zero elements are skipped (left 0)
 inline void batch_inv(std::vector<fe> &a) {
   size_t n = a.size();

@@ -114,7 +114,7 @@ enum kh_walk_mode {
   // P2SH-P2WPKH script hash hash160(00 14 || h) against the same filter (KH_MODE_P2SH)
   KM_P2SH = 32,
 };
-// device hit kinds: base kind (0: 02||X, 1: 03||X, 2: 04||X||Y, 3: xpoint, 4: bsgs, 5: eth) plus, with
+// device hit kinds: base kind (0: 02||X, 1: 03||X, 2: 04||X||Y, 3: xpoint, 4: bsgs, 5: eth, 6: taproot) plus, with
 // KM_ENDO, the image e (0: X, 1: beta*X, 2: beta^2*X) << 4 and, for 04 hashes, the Y sign << 6
 #define KH_DKIND_ENDO_SHIFT 4
 #define KH_DKIND_NEG 0x40u
@@ -242,9 +242,30 @@ struct mini_keys_args {
   uint32_t *out13;     // parity hook (or null): per entry the key's 8 words and the hash160's 5, as bytes in memory
 };
 
+// Taproot key-path targets (BIP-341 / BIP-86, k_tap_keys).  Per point P = (x, y) of a KM_DUMP walk: the
+// tweak t = SHA-256_TapTweak(x) read big-endian (a t >= n is skipped, as BIP-341 fails there), P' = P with
+// its Y made even, Q = P' + t*G (comb, Jacobian), one inversion per lane for its KH_TAP_BATCH points, then
+// Q.x[0..20) against a blocked target filter; device hit kind KH_DKIND_TAPROOT, idx = idx0 + the point's index
+#define KH_TAP_BATCH 8
+#define KH_DKIND_TAPROOT 6u
+struct tap_keys_args {
+  const uint32_t *xs, *ys;  // n points in the KM_DUMP layout: 8 LE limbs per coordinate, point i at word 8*i
+  uint32_t n;
+  uint64_t idx0;            // the job's index of point 0
+  const uint32_t *comb;
+  const uint4 *tblk;        // null: no probe (parity hook)
+  uint32_t tblocks;
+  uint32_t *hit_count;
+  kh_dev_hit *hits;
+  uint32_t hit_cap;
+  uint32_t *out8;           // parity hook (or null): per point Q.x as its 32 big-endian bytes in memory; a
+                            // skipped point's 8 words are left as they were
+};
+
 namespace kh {
 hipError_t launch_mini_filter(const mini_filter_args &A, hipStream_t st);
 hipError_t launch_mini_keys(const mini_keys_args &A, hipStream_t st);
+hipError_t launch_tap_keys(const tap_keys_args &A, hipStream_t st);
 hipError_t launch_walk(int mode, const walk_args &A, hipStream_t st, int H = KH_WALK_H);
 // The sparse-pad walks -- the BSGS giant walks and -m xpoint against the blocked target filter -- keep
 // only the even prefix products in the inversion pad (kh_kernels.hip k_walk)

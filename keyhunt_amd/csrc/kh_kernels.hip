@@ -1291,6 +1291,86 @@ __global__ void __launch_bounds__(64) k_mini_keys(mini_keys_args A) {
 }
 
 // ------------------------------------------------------------------------------------------
+// Taproot key-path targets (BIP-341): the output key Q = P' + t*G of every point P a KM_DUMP walk wrote.
+// KH_TAP_BATCH points per lane, point e = t*T + g for the lane's slot t.  Forward: the tweak (one SHA-256
+// compression on the TapTweak midstate; t >= n skips the point), P' = P with Y made even, Q in Jacobian
+// coordinates, running product of the Z's.  One inversion, then backward: Q.x = X / Z^2 and its first 20
+// bytes against the blocked filter of the programs.  t*G = +-P' (chance 2^-255) leaves Z = 0 and the point
+// is skipped: the host confirms every hit, so nothing depends on what such a point would report.
+// Bounded to 4 waves/SIMD (128 VGPRs, 2 of them spilled): unbounded it takes 135 and fits 3 (DESIGN.md 2
+// "Taproot targets" has the resource table and the measured A/B of batch and bound).
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64, 4) k_tap_keys(tap_keys_args A) {
+  const uint32_t T = gridDim.x * blockDim.x;
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  fe px[KH_TAP_BATCH], pz[KH_TAP_BATCH], pre[KH_TAP_BATCH];
+  uint32_t live = 0;
+  fe acc;
+  fe_set_u32(acc, 1);
+#pragma unroll 1
+  for (uint32_t t = 0; t < KH_TAP_BATCH; t++) {
+    const uint64_t e = (uint64_t)t * T + g;
+    pre[t] = acc;
+    if (e >= A.n) continue;
+    ge p;
+    load_fe(p.x, A.xs + e * 8);
+    load_fe(p.y, A.ys + e * 8);
+    uint32_t st[8];
+    taptweak_hash(p.x, st);
+    // the digest read big-endian as 8 LE limbs; t >= n (no borrow from t - n) has no output key
+    uint32_t s[8], bo = 0, nz = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      s[i] = st[7 - i];
+      nz |= s[i];
+      (void)subb(s[i], order_limb(i), bo, bo);
+    }
+    if (!bo) continue;
+    if (p.y.d[0] & 1u) fe_neg(p.y, p.y);
+    gej Q;
+    if (nz) {
+      comb_mult_jac(Q, s, A.comb);
+    } else {
+      Q.inf = true;
+    }
+    gej_add_ge(Q, p);
+    if (fe_is_zero(Q.z)) continue;
+    px[t] = Q.x;
+    pz[t] = Q.z;
+    fe_mul(acc, acc, Q.z);
+    live |= 1u << t;
+  }
+  if (!live) return;
+  fe inv;
+  fe_inv(inv, acc);
+#pragma unroll 1
+  for (int t = KH_TAP_BATCH - 1; t >= 0; t--) {
+    if (!((live >> t) & 1u)) continue;
+    fe zi, zi2, x;
+    fe_mul(zi, inv, pre[t]);
+    fe_mul(inv, inv, pz[t]);
+    fe_sqr(zi2, zi);
+    fe_mul(x, px[t], zi2);
+    const uint64_t e = (uint64_t)t * T + g;
+    uint32_t w[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) w[j] = bswap32(x.d[7 - j]);
+    if (A.out8) {
+#pragma unroll
+      for (int j = 0; j < 8; j++) A.out8[e * 8 + j] = w[j];
+    }
+    if (A.tblk && tblk_probe_at(A.tblk, A.tblocks, w)) {
+      const uint32_t slot = atomicAdd(A.hit_count, 1u);
+      if (slot < A.hit_cap) {
+        A.hits[slot].idx = A.idx0 + e;
+        A.hits[slot].kind = KH_DKIND_TAPROOT;
+        A.hits[slot].aux = 0;
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // Parity-test kernels (exercised by tests/ through the C-ABI): hash160 and bloom probes of
 // given inputs, field ops.
 // ------------------------------------------------------------------------------------------
@@ -1583,6 +1663,12 @@ hipError_t launch_mini_filter(const mini_filter_args &A, hipStream_t st) {
 hipError_t launch_mini_keys(const mini_keys_args &A, hipStream_t st) {
   const uint32_t lanes = (A.n + KH_MINI_BATCH - 1) / KH_MINI_BATCH;
   hipLaunchKernelGGL(k_mini_keys, dim3((lanes + 63) / 64), dim3(64), 0, st, A);
+  return hipGetLastError();
+}
+
+hipError_t launch_tap_keys(const tap_keys_args &A, hipStream_t st) {
+  const uint32_t lanes = (A.n + KH_TAP_BATCH - 1) / KH_TAP_BATCH;
+  hipLaunchKernelGGL(k_tap_keys, dim3((lanes + 63) / 64), dim3(64), 0, st, A);
   return hipGetLastError();
 }
 

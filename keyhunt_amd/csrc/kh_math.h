@@ -981,6 +981,25 @@ KH_HD void hash160_uncomp(const fe &x, const fe &y, uint32_t out[5]) {
   ripemd160_32(m, out);
 }
 
+// BIP-341's key-path tweak of an internal key x: SHA-256(tag || tag || x) with tag = SHA-256("TapTweak").
+// tag || tag is exactly one block, so its compression is the constant below and a tweak costs one
+// compression, over x || 80 00 ... || the length 768 bits.  st: the digest's 8 big-endian words.
+KH_HD void taptweak_hash(const fe &x, uint32_t st[8]) {
+  const uint32_t MID[8] = {0xd129a2f3u, 0x701c655du, 0x6583b6c3u, 0xb9419727u,
+                           0x95f4e232u, 0x94fd54f4u, 0xa2ae8d85u, 0x47ca590bu};
+  uint32_t w[16];
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    st[i] = MID[i];
+    w[i] = x.d[7 - i];
+  }
+  w[8] = 0x80000000u;
+#pragma unroll
+  for (int i = 9; i < 15; i++) w[i] = 0;
+  w[15] = 96 * 8;
+  sha256_transform(st, w);
+}
+
 // ------------------------------------------------------------------------------------------
 // XXH64 for the two input shapes on the hot path (xxhash/xxhash.h:2468-2529).
 // ------------------------------------------------------------------------------------------

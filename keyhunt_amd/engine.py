@@ -22,6 +22,7 @@ KH_MODE_ENDO = 0x10  # OR into mode: -e
 KH_MODE_P2SH = 0x20  # OR into KH_MODE_ADDRESS: also probe the nested P2SH-P2WPKH digest of each 02/03 hash
 KH_SEARCH_COMPRESS, KH_SEARCH_UNCOMPRESS, KH_SEARCH_BOTH = 0, 1, 2
 KH_KIND_02, KH_KIND_03, KH_KIND_04, KH_KIND_XPOINT, KH_KIND_ETH = 0, 1, 2, 3, 5
+KH_KIND_TAPROOT = 6  # taproot_scan: the point's taproot output key matched a witness program
 KH_KIND_ENDO1, KH_KIND_ENDO2, KH_KIND_NEGY = 0x10, 0x20, 0x40
 KH_KIND_P2SH = 0x80  # with KH_MODE_P2SH, OR'ed into KH_KIND_02/03: the nested digest matched
 TIME_ADDRESS, TIME_XPOINT, TIME_BSGS, TIME_BUILD, TIME_SETUP = 0, 1, 2, 3, 4
@@ -65,7 +66,8 @@ class KhMinikeyHit(ctypes.Structure):
 
 MINIKEY_ALPHABET = "123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz"
 TIME_MINI_FILTER, TIME_MINI_KEYS = 5, 6
-KH_E_STATE, KH_E_OVERFLOW = -4, -5
+TIME_TAP_KEYS = 7
+KH_E_ARG, KH_E_STATE, KH_E_OVERFLOW, KH_E_RANGE = -1, -4, -5, -7
 
 _lib = None
 
@@ -154,6 +156,12 @@ def lib() -> ctypes.CDLL:
     L.kh_minikeys_valid.argtypes = [P, u8p, ctypes.c_uint64, u64p, ctypes.c_uint64, u64p]
     L.kh_minikeys_keys.argtypes = [P, u8p, u64p, ctypes.c_uint32, u8p]
     L.kh_minikeys_queue.argtypes = [P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+    L.kh_taproot_set_targets.argtypes = [P, u8p, ctypes.c_uint64]
+    L.kh_taproot_scan.argtypes = [P, u8p, u8p, ctypes.c_uint64, ctypes.POINTER(KhHit), ctypes.c_uint32,
+                                  ctypes.POINTER(ctypes.c_uint32)]
+    L.kh_taproot_set_window.argtypes = [P, ctypes.c_uint64]
+    L.kh_taproot_outputs.argtypes = [P, u8p, ctypes.c_uint32, u8p]
+    L.kh_taproot_stats.argtypes = [P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
     _lib = L
     return L
 
@@ -344,6 +352,45 @@ class Engine:
         """(device queue entries, times the last minikeys call grew the queue and redid a window)."""
         a, b = ctypes.c_uint32(), ctypes.c_uint32()
         self._chk(lib().kh_minikeys_queue(self._ctx, ctypes.byref(a), ctypes.byref(b)), "kh_minikeys_queue")
+        return a.value, b.value
+
+    # -- taproot -------------------------------------------------------------------------------
+    def taproot_set_targets(self, progs: list[bytes]) -> None:
+        """The 32-byte witness programs of bc1p... addresses (kept beside set_targets' rows)."""
+        assert all(len(p) == 32 for p in progs)
+        self._chk(lib().kh_taproot_set_targets(self._ctx, b"".join(progs), len(progs)), "kh_taproot_set_targets")
+
+    def taproot_scan_status(self, start: int, n_keys: int, stride: int = 1, cap: int = 4096):
+        """kh_taproot_scan returning (status, hits, n_hits) instead of raising."""
+        hits = (KhHit * max(cap, 1))()
+        n = ctypes.c_uint32(0)
+        r = lib().kh_taproot_scan(self._ctx, be32(start), be32(stride), n_keys, hits, cap, ctypes.byref(n))
+        return r, [ScanHit(int.from_bytes(bytes(h.key), "big"), h.offset, h.kind, bool(h.compressed))
+                   for h in hits[: min(n.value, cap)]], n.value
+
+    def taproot_scan(self, start: int, n_keys: int, stride: int = 1, cap: int = 4096) -> list[ScanHit]:
+        """Keys start + i*stride whose key-path taproot output key is a program of taproot_set_targets, in
+        offset order; a hit's key is the BIP-340 secret key of the internal key (n - k where P.y is odd)."""
+        r, out, _ = self.taproot_scan_status(start, n_keys, stride, cap)
+        self._chk(r, "kh_taproot_scan")
+        return out
+
+    def taproot_set_window(self, points: int = 0) -> None:
+        """Points per window of taproot_scan (a multiple of 1024, at most 2^24; 0 = the default 2^24)."""
+        self._chk(lib().kh_taproot_set_window(self._ctx, points), "kh_taproot_set_window")
+
+    def taproot_outputs(self, points: list[tuple[int, int]]) -> list[bytes]:
+        """Per point (x, y) the 32-byte output key as the tweak kernel computes it (zeros: t >= n)."""
+        n = len(points)
+        out = ctypes.create_string_buffer(32 * n)
+        buf = b"".join(be32(x) + be32(y) for x, y in points)
+        self._chk(lib().kh_taproot_outputs(self._ctx, buf, n, out), "kh_taproot_outputs")
+        return [out.raw[32 * i:32 * i + 32] for i in range(n)]
+
+    def taproot_stats(self) -> tuple[int, int]:
+        """(the tweak kernel's compiled batch, filter hits the device reported in the last taproot_scan)."""
+        a, b = ctypes.c_uint32(), ctypes.c_uint32()
+        self._chk(lib().kh_taproot_stats(self._ctx, ctypes.byref(a), ctypes.byref(b)), "kh_taproot_stats")
         return a.value, b.value
 
     # -- BSGS ----------------------------------------------------------------------------------

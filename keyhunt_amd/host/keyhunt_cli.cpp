@@ -31,6 +31,7 @@
 
 #include "kh_gpu.h"
 #include "../csrc/kh_math.h"
+#include "../csrc/kh_host.h"
 #include "kh_bsgs_files.h"
 #include "kh_host_util.h"
 #include "kh_mapped.h"
@@ -93,9 +94,14 @@ struct options {
   // --segwit (-m address; the reference has no such option): bc1q... lines are targets, a 3... line
   // turns the nested P2SH-P2WPKH probes on (KH_MODE_P2SH), hits print their segwit forms
   bool segwit = false;
+  // --taproot (-m address; the reference has no such option): bc1p... lines are targets, searched by
+  // kh_taproot_scan after each chunk's kh_scan.  Key-path-only outputs (BIP-86, no script tree) only.
+  bool taproot = false;
 } opt;
 // --segwit: what the target reader saw -- bech32 P2WPKH rows, base58 lines of version byte 05
 uint64_t g_seg_bech32 = 0, g_seg_p2sh = 0;
+// --taproot: the 32-byte witness programs of the file's bc1p... lines
+std::vector<uint8_t> g_tap_progs;
 // keyhunt.cpp:419; ggsb and angrygiant walk like sequential (ggsb with BSGS_STEP = 2 x block size)
 const char *BSGS_MODES[7] = {"sequential", "backward", "both", "random", "dance", "ggsb", "angrygiant"};
 enum { BM_SEQUENTIAL, BM_BACKWARD, BM_BOTH, BM_RANDOM, BM_DANCE, BM_GGSB, BM_ANGRYGIANT };
@@ -148,6 +154,21 @@ void writekey(kh_ctx *ctx, bool compressed, const uint8_t key[32], bool nested =
   emit_hit("KEYFOUNDKEYFOUND.txt", "\nHit! ",
            "Private Key: " + h.k + "\npubkey: " + h.pub + "\nAddress " + rmd_to_address(h.rmd, nested ? 5 : 0) + "\nrmd160 " +
                hex(h.rmd, 20) + "\n" + fifth);
+}
+
+// --taproot: a kh_taproot_scan hit.  The key is the BIP-340 secret key of the internal key, so its public
+// key has an even Y and prints as 02 || X; the address is the bech32m form of the output key, which takes
+// rmd160's line.
+void write_taproot_key(kh_ctx *ctx, const uint8_t key[32]) {
+  const hit_text h(ctx, key, true);
+  fe x, y;
+  fe_from_be(x, h.xy);
+  fe_from_be(y, h.xy + 32);
+  uint8_t q[32];
+  if (!kh_host::taproot_output_x(x, y, q)) return;  // a confirmed hit has an output key
+  emit_hit("KEYFOUNDKEYFOUND.txt", "\nHit! ",
+           "Private Key: " + h.k + "\npubkey: " + h.pub + "\nAddress " + bech32m_p2tr_encode(q) + "\ntaproot output key " +
+               hex(q, 32) + "\n");
 }
 
 // keyhunt.cpp:6925-6950: Ethereum hits
@@ -278,6 +299,7 @@ std::vector<std::string> fgets_pieces(FILE *f, size_t cap) {
 bool read_targets(const char *fn, int mode, std::vector<uint8_t> &rows, uint64_t &bloom_items,
                   std::vector<uint8_t> *adds = nullptr) {
   g_seg_bech32 = g_seg_p2sh = 0;  // --segwit: the counts describe the file read by this call alone
+  g_tap_progs.clear();
   FILE *f = fopen(fn, "r");
   if (!f) {
     fprintf(stderr, "[E] Error opening the file %s\n", fn);
@@ -332,6 +354,11 @@ bool read_targets(const char *fn, int mode, std::vector<uint8_t> &rows, uint64_t
       rows.insert(rows.end(), raw, raw + 20);
       if (adds) adds->insert(adds->end(), raw, raw + 20);
       g_seg_bech32++;
+      ok = true;
+    }
+    if (opt.taproot && r == 62 && bech32m_p2tr_decode(ln.c_str(), raw)) {
+      // --taproot: a mainnet P2TR address; its witness program is an output key, no row of the table
+      g_tap_progs.insert(g_tap_progs.end(), raw, raw + 32);
       ok = true;
     }
     if (r > 0 && r <= 40) {
@@ -506,6 +533,7 @@ int open_with_targets(addr_job *j, kh_ctx **out) {
     r = kh_targets_load(ctx, j->data_file, opt.skip_checksum ? KH_LOAD_SKIP_CHECKSUM : 0);
   else
     r = kh_set_targets(ctx, j->rows->data(), j->rows->size() / 20, j->bloom_items);
+  if (!r && !g_tap_progs.empty()) r = kh_taproot_set_targets(ctx, g_tap_progs.data(), g_tap_progs.size() / 32);
   if (!r && j->save_data) {
     printf("[D] size data %llu\n", (unsigned long long)(j->rows->size()));  // keyhunt.cpp:7773
     printf("[+] Writing file %s ........\n", j->data_file);
@@ -658,7 +686,10 @@ void addr_worker(addr_job *j) {
     }
     u_to_be32(base, st_be);
     uint32_t nh = 0;
-    r = kh_scan(ctx, st_be, stride_be, j->nseq, j->mode, (uint32_t)opt.search, hits.data(), (uint32_t)hits.size(), &nh);
+    // --taproot: a file of bc1p... lines alone has no row for kh_scan to look for
+    const bool plain = !opt.taproot || !j->rows->empty();
+    if (plain)
+      r = kh_scan(ctx, st_be, stride_be, j->nseq, j->mode, (uint32_t)opt.search, hits.data(), (uint32_t)hits.size(), &nh);
     if (r == KH_E_OVERFLOW && nh > hits.size()) {  // a short vanity prefix: take them all
       hits.resize(nh);
       r = kh_scan(ctx, st_be, stride_be, j->nseq, j->mode, (uint32_t)opt.search, hits.data(), (uint32_t)hits.size(), &nh);
@@ -680,6 +711,18 @@ void addr_worker(addr_job *j) {
     if (r) {
       fprintf(stderr, "[E] kh_scan: %s (%s)\n", kh_strerror(r), kh_last_error(ctx));
       break;
+    }
+    if (!g_tap_progs.empty()) {  // --taproot: the same chunk's keys against the bc1p... programs
+      r = kh_taproot_scan(ctx, st_be, stride_be, j->nseq, hits.data(), (uint32_t)hits.size(), &nh);
+      if (r == KH_E_OVERFLOW && nh > hits.size()) {
+        hits.resize(nh);
+        r = kh_taproot_scan(ctx, st_be, stride_be, j->nseq, hits.data(), (uint32_t)hits.size(), &nh);
+      }
+      if (r) {
+        fprintf(stderr, "[E] kh_taproot_scan: %s (%s)\n", kh_strerror(r), kh_last_error(ctx));
+        break;
+      }
+      for (uint32_t i = 0; i < nh; i++) write_taproot_key(ctx, hits[i].key);
     }
     g_groups_done += (j->nseq + group - 1) / group;
   }
@@ -1276,7 +1319,9 @@ void usage(const char *p) {
   printf("Usage: %s -m address|rmd160|xpoint|bsgs -f FILE [-b BITS | -r START:END] [-l compress|uncompress|both]\n"
          "       [-n N] [-k K] [-I STRIDE] [-g GPUS] [-q] [-s SECONDS] [-M] [-L blocked|reference]\n"
          "       [-e] [-c btc|eth] [-R] [-B sequential|backward|both|random|dance|angrygiant] [-S] [-6]\n"
-         "       [-z MULT] [-m vanity -v PREFIX ...] [--rmd-batch-size N] [--segwit] [-d] [-h]\n"
+         "       [-z MULT] [-m vanity -v PREFIX ...] [--rmd-batch-size N] [--segwit] [--taproot] [-d] [-h]\n"
+         "       --taproot (-m address): bc1p... lines of FILE are targets.  Only key-path-only outputs (BIP-86, no\n"
+         "       script tree) can be found; a hit's key is the BIP-340 key of the internal key (tr(KEY)).\n"
 #ifdef KH_WITH_MINIKEYS
          "       -m minikeys -f FILE [-C MINIKEY] [-8 ALPHABET] [-n N] [-R]\n"
 #endif
@@ -1312,6 +1357,7 @@ bool parse_options(int argc, char **argv, int &status) {
                                            {"tmpdir", required_argument, 0, 14},
                                            {"rmd-batch-size", required_argument, 0, 15},
                                            {"segwit", no_argument, 0, 16},
+                                           {"taproot", no_argument, 0, 17},
                                            {0, 0, 0, 0}};
   // --mapped-size / --bloom-bytes / --create-mapped N: the entry count and error the byte budget
   // allows (bloom_entries_for_bytes, keyhunt.cpp:7510-7530)
@@ -1410,6 +1456,7 @@ bool parse_options(int argc, char **argv, int &status) {
         opt.rmd_batch = (int)v;
         break;
       }
+      case 17: opt.taproot = true; break;  // -m address: bc1p... targets (checked in check_options)
       case 16: opt.segwit = true; break;  // -m address: bech32 and P2SH-P2WPKH targets (checked in check_options)
       case 'm': {
         int m = -1;
@@ -1592,6 +1639,19 @@ bool check_options() {
       return false;
     }
   }
+  // --taproot: -m address with bitcoin targets; no -e (each image would need its own tweak) and no -S (the
+  // data_<hex>.dat cache keeps 20-byte rows only)
+  if (opt.taproot) {
+    const char *why = opt.mode != MODE_ADDRESS ? "--taproot works with -m address only"
+                      : opt.eth                ? "--taproot doesn't work with -c eth"
+                      : opt.endo               ? "--taproot doesn't work with -e (each image would need its own tweak)"
+                      : opt.save_read          ? "--taproot doesn't work with -S (the data file keeps no witness programs)"
+                                               : nullptr;
+    if (why) {
+      fprintf(stderr, "[E] %s\n", why);
+      return false;
+    }
+  }
   if (opt.stride_set) printf("[+] Stride : %s\n", u_dec(opt.stride).c_str());  // keyhunt.cpp:1195-1203
   if (opt.mode == MODE_BSGS) printf("[+] Mode BSGS %s\n", BSGS_MODES[opt.bsgs_mode]);  // keyhunt.cpp:1209-1211
   if (opt.mode == MODE_ADDRESS && !opt.crypto_given) printf("[+] Setting search for btc adddress\n");  // 1217-1220
@@ -1743,6 +1803,7 @@ int run_address_family(run &R) {
   if (opt.segwit)
     printf("[+] Segwit targets: %llu bech32, %llu P2SH-P2WPKH\n", (unsigned long long)g_seg_bech32,
            (unsigned long long)g_seg_p2sh);
+  if (opt.taproot) printf("[+] Taproot targets: %llu\n", (unsigned long long)(g_tap_progs.size() / 32));
   if (opt.mapped) {
     bool ok;
     if (opt.mode == MODE_VANITY) {  // the vanity bloom: the first min_bytes bytes of every A

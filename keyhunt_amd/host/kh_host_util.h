@@ -528,6 +528,66 @@ inline std::string bech32_p2wpkh_encode(const uint8_t prog[20]) {
   return s;
 }
 
+// BIP-350 bech32m for mainnet P2TR (--taproot): "bc1p" + the 32-byte witness program of version 1 as 52
+// five-bit groups (256 bits and 4 zero padding bits) + a 6-group checksum whose polymod constant is
+// 0x2bc830a3.  62 characters, all lower case or all upper case.
+inline const uint32_t BECH32M_CONST = 0x2bc830a3u;
+inline bool bech32m_p2tr_decode(const char *s, uint8_t prog[32]) {
+  if (strlen(s) != 62) return false;
+  bool lower = false, upper = false;
+  uint8_t v[5 + 59] = {3, 3, 0, 2, 3};
+  char c[62];
+  for (int i = 0; i < 62; i++) {
+    lower |= s[i] >= 'a' && s[i] <= 'z';
+    upper |= s[i] >= 'A' && s[i] <= 'Z';
+    c[i] = (s[i] >= 'A' && s[i] <= 'Z') ? (char)(s[i] - 'A' + 'a') : s[i];
+  }
+  if (lower && upper) return false;
+  if (c[0] != 'b' || c[1] != 'c' || c[2] != '1') return false;
+  for (int i = 0; i < 59; i++) {
+    const char *p = c[3 + i] ? strchr(BECH32, c[3 + i]) : nullptr;
+    if (!p) return false;
+    v[5 + i] = (uint8_t)(p - BECH32);
+  }
+  if (bech32_polymod(v, sizeof v) != BECH32M_CONST) return false;
+  if (v[5] != 1) return false;  // witness version 1
+  // 52 groups of 5 bits -> 32 bytes and 4 padding bits, which must be zero
+  uint32_t acc = 0;
+  int bits = 0, o = 0;
+  for (int i = 0; i < 52; i++) {
+    acc = (acc << 5) | v[6 + i];
+    bits += 5;
+    if (bits >= 8) {
+      bits -= 8;
+      prog[o++] = (uint8_t)(acc >> bits);
+      acc &= (1u << bits) - 1u;
+    }
+  }
+  return o == 32 && bits == 4 && acc == 0;
+}
+inline std::string bech32m_p2tr_encode(const uint8_t prog[32]) {
+  uint8_t v[5 + 59] = {3, 3, 0, 2, 3};
+  v[5] = 1;
+  uint32_t acc = 0;
+  int bits = 0, o = 6;
+  for (int i = 0; i < 32; i++) {
+    acc = (acc << 8) | prog[i];
+    bits += 8;
+    while (bits >= 5) {
+      bits -= 5;
+      v[o++] = (uint8_t)((acc >> bits) & 31u);
+    }
+    acc &= (1u << bits) - 1u;
+  }
+  v[o++] = (uint8_t)((acc << (5 - bits)) & 31u);  // the last 1 bit and 4 zero padding bits
+  for (int i = 0; i < 6; i++) v[58 + i] = 0;
+  const uint32_t pm = bech32_polymod(v, sizeof v) ^ BECH32M_CONST;
+  for (int i = 0; i < 6; i++) v[58 + i] = (uint8_t)((pm >> (5 * (5 - i))) & 31u);
+  std::string s = "bc1";
+  for (int i = 0; i < 59; i++) s += BECH32[v[5 + i]];
+  return s;
+}
+
 // addvanity (keyhunt.cpp:6739-6866): the hash160 ranges [A_j, B_j] of the addresses that start
 // with `target` (padded with '1' for A, 'z' for B up to each 25-byte decoding length), appended to
 // `ranges` (40 bytes each); min_bytes tracks the common-prefix length the vanity bloom keys on.
