@@ -11,6 +11,8 @@
  *                         + initBloomFilter 7605-7626 + _sort 1359-1364
  *   kh_minikeys_scan   <- thread_process_minikeys, one chunk of N valid minikeys  keyhunt.cpp:3184-3255
  *   kh_taproot_scan    <- nothing: the reference has no taproot search (its TODO lists bech32 addresses)
+ *   kh_kang_solve      <- nothing in the reference: its README sends public-key puzzles this wide to "another
+ *                         tools like kangaroo"
  *   kh_bsgs_setup      <- BSGS parameter block                            keyhunt.cpp:1454-1842
  *   kh_bsgs_build      <- thread_bPload / thread_bPload_2blooms + bsgs_sort keyhunt.cpp:5284-5644, 2466-2503
  *   kh_bsgs_scan       <- thread_process_bsgs (sequential), bases of 2N   keyhunt.cpp:4549-4888
@@ -41,7 +43,8 @@ extern "C" {
 #define KH_E_STATE -4      /* call out of order (e.g. scan before targets) */
 #define KH_E_OVERFLOW -5   /* caller's output array too small (count is still reported) */
 #define KH_E_BSGS_N -6     /* BSGS: n has no exact square root / sqrt(n) not a multiple of 1024 */
-#define KH_E_RANGE -7      /* BSGS: range smaller than N ("[E] the given range is small") */
+#define KH_E_RANGE -7      /* BSGS: range smaller than N ("[E] the given range is small"); kangaroo: width outside
+                              [2^16, 2^192) or a range that reaches the group order */
 #define KH_E_IO -8         /* table file missing, short or not writable (see kh_last_error) */
 #define KH_E_FORMAT -9     /* table file of another N/k, or its sha256 checksum does not match */
 
@@ -246,6 +249,71 @@ int kh_taproot_outputs(kh_ctx *ctx, const uint8_t *xy, uint32_t n, uint8_t *out3
  * device reported in the last kh_taproot_scan, before the host's confirmation */
 int kh_taproot_stats(kh_ctx *ctx, uint32_t *batch, uint32_t *device_hits);
 
+/* ---- kangaroo ----------------------------------------------------------------------------- */
+/* Pollard's lambda method for one target Q whose key lies in a known interval [a, b] of width W = b - a: about
+ * 2*sqrt(W) group operations and almost no memory, where BSGS time grows with W itself.  With Q' = Q - a*G
+ * (key k' = k - a in [0, W]) a herd of N kangaroos jumps P += J[x(P) mod 32], dist += d[x(P) mod 32] over 32
+ * fixed jumps J[j] = d_j*G.  An even index is TAME, P = dist*G; an odd one WILD, P = Q' + dist*G.  A point
+ * whose x has its top dp_bits bits zero is DISTINGUISHED and goes to a host table keyed on x; a tame and a
+ * wild meeting there give k' = t - w or -(t + w).  Distances are plain 256-bit integers that never wrap
+ * (W < 2^192).  All 32-byte values are big-endian. */
+#define KH_KANG_TAME 0
+#define KH_KANG_WILD 1
+#define KH_KANG_STALL 0x10  /* OR'ed into kind: the kangaroo sits on +-J[j] (or its point could not be formed) and
+                               does not move; kh_kang_add_dps places it afresh */
+#define KH_KANG_DP_AUTO 0xffffffffu
+typedef struct { uint8_t x[32], dist[32]; uint32_t index, kind; } kh_kang_dp;
+typedef struct { uint64_t jumps, dps, same_herd, reseeds, stalls, lost, bad; } kh_kang_stats;
+/* Target pub_xy = {x[32], y[32]}, inclusive range [start, end].  KH_E_RANGE: end < start, W < 2^16, W >= 2^192,
+ * or end reaches the group order; KH_E_ARG: Q not on the curve, or a bad jump.  Q = start*G records the key
+ * `start` as found (kh_kang_solve returns it) and nothing is ever launched.  jumps_or_null: 32 distances of
+ * 32 bytes, each non-zero and below 2^128; NULL: with jb = floor(bitlen(W)/2) + 1, d_j = SHA-256(
+ * "kh-kangaroo-jump" || byte j || byte jb) mod 2^jb, a 0 made 1, a value equal to an earlier one incremented
+ * until it is distinct.  dp_bits: 0..32, or KH_KANG_DP_AUTO: the largest dp with N*2^dp <= sqrt(W)/8 once the
+ * herd's size N is known.  Drops the previous search's herd, table and statistics. */
+int kh_kang_setup(kh_ctx *ctx, const uint8_t pub_xy[64], const uint8_t start[32], const uint8_t end[32],
+                  uint32_t dp_bits, const uint8_t *jumps_or_null);
+/* the 32 jump distances in use */
+int kh_kang_jumps(kh_ctx *ctx, uint8_t out[32 * 32]);
+/* kangaroos per lane that share one inversion (KH_KANG_BATCH as built), jumps per kangaroo per launch (unless
+ * set: the largest power of two up to 256 that keeps a launch of the whole herd below sqrt(W)/16 jumps), the
+ * herd's size (0: none yet) and the dp_bits in use (KH_KANG_DP_AUTO until a herd exists); any pointer may be
+ * null */
+int kh_kang_geometry(kh_ctx *ctx, uint32_t *batch, uint32_t *steps_per_launch, uint32_t *herd, uint32_t *dp_bits);
+/* jumps per kangaroo per launch for the following steps (0 = automatic, see kh_kang_geometry) */
+int kh_kang_set_launch(kh_ctx *ctx, uint32_t steps_per_launch);
+/* A herd of `total` kangaroos (1..2^24; a first call, or another total, resizes the herd and empties the table):
+ * kangaroos first .. first+n-1 are placed at dists (n x 32 bytes) through the lane-setup kernel.  KH_E_ARG: a
+ * tame distance of 0, first + n > total.  A wild with dist*G = +-Q' has no point: it is marked stalled and
+ * the next step reports it. */
+int kh_kang_set_herd(kh_ctx *ctx, uint32_t total, uint32_t first, uint32_t n, const uint8_t *dists);
+/* The same with the library's distances for all n_kangaroos (0: the default herd, never more than sqrt(W)/128
+ * rounded down to a power of two -- a sixteenth of the sqrt(W)/8 bound, so that the automatic dp_bits is 4 or
+ * more -- and at least 64): with h = SHA-256(seed u64 LE || index u32 LE || generation u32
+ * LE) read big-endian, a tame starts at floor(W/2) + h mod (W+1), a wild at 1 + h mod W.  The generation is 0
+ * and grows by one each time kh_kang_add_dps places the kangaroo afresh.  Empties table and statistics. */
+int kh_kang_seed(kh_ctx *ctx, uint64_t seed, uint32_t n_kangaroos);
+/* Every kangaroo makes `steps` jumps (in launches of steps_per_launch).  dps: the distinguished points and
+ * stall records (one per stalled kangaroo and call, however many launches), in any order, at most cap of them (which also bounds what the device writes); *lost = how
+ * many more there were.  The herd has advanced either way. */
+int kh_kang_step(kh_ctx *ctx, uint32_t steps, kh_kang_dp *dps, uint32_t cap, uint32_t *n_dps, uint64_t *lost);
+/* parity hook: the points {x[32], y[32]} and distances of kangaroos first .. first+n-1 (either may be null) */
+int kh_kang_get_herd(kh_ctx *ctx, uint32_t first, uint32_t n, uint8_t *xy, uint8_t *dist);
+/* Feed n records to the context's table, which takes them in (index, dist) order whatever order they come
+ * in (a host with several contexts feeds one table this way).  Same x, other kind: the collision is resolved (kh_kang_resolve; neither candidate: `bad`).  Same
+ * x, same kind, another index: `same_herd`, and the kangaroo of the record that came later is placed afresh
+ * at its next generation; so is a stalled one.  The rest of a call's records of a kangaroo placed afresh are
+ * dropped.  *found = 1 and key once the key is known. */
+int kh_kang_add_dps(kh_ctx *ctx, const kh_kang_dp *dps, uint32_t n, uint8_t key[32], uint32_t *found);
+/* context-free, host only: k' = t - w or -(t + w) (mod n), k = start + k'; 1 and the key for the candidate with
+ * k*G = Q, else 0 */
+int kh_kang_resolve(const uint8_t tame_dist[32], const uint8_t wild_dist[32], const uint8_t start[32],
+                    const uint8_t pub_xy[64], uint8_t key[32]);
+/* step -> add_dps -> place afresh, until the key is found or at least max_jumps more jumps are done (whole
+ * launches); a following call continues.  Seeds the default herd (seed 0) when there is none.  stats (or null):
+ * the totals since kh_kang_setup / kh_kang_seed. */
+int kh_kang_solve(kh_ctx *ctx, uint64_t max_jumps, uint8_t key[32], uint32_t *found, kh_kang_stats *stats);
+
 /* ---- BSGS --------------------------------------------------------------------------------- */
 /* layer-1 layout for the next kh_bsgs_setup (KH_LAYER1_BLOCKED unless changed) */
 int kh_bsgs_set_layer1(kh_ctx *ctx, uint32_t layout);
@@ -306,7 +374,8 @@ int kh_bsgs_refine_stats(kh_ctx *ctx, uint64_t *first_level, uint64_t *second_le
 /* Accumulated device time of walk launches of one kind since the last reset, measured with
  * HIP events on the context's stream.  kind: 0 address/rmd160, 1 xpoint, 2 bsgs giant,
  * 3 bsgs build, 4 lane setup (scalar mult), 5 minikeys filter (points = candidates), 6 minikeys keys
- * (points = valid candidates), 7 taproot tweak kernel (kh_taproot_scan's walks count under 0 and 4). */
+ * (points = valid candidates), 7 taproot tweak kernel (kh_taproot_scan's walks count under 0 and 4),
+ * 8 kangaroo walk (points = jumps; the herds' placement counts under 4). */
 int kh_kernel_time(kh_ctx *ctx, uint32_t kind, uint64_t *launches, double *ms, uint64_t *points);
 int kh_kernel_time_reset(kh_ctx *ctx);
 

@@ -423,6 +423,7 @@ int kh_release_walk(kh_ctx *ctx) {
   (void)hipDeviceSynchronize();
   ctx->release_lanes();
   ctx->cont_valid = false;
+  ctx->kang = kang_state();  // the kangaroo search's herd, table and buffers
   return KH_OK;
 }
 

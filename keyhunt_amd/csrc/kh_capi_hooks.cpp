@@ -240,7 +240,7 @@ int kh_bsgs_refine_masks(kh_ctx *ctx, uint32_t target, const uint8_t start[32], 
 }
 
 int kh_kernel_time(kh_ctx *ctx, uint32_t kind, uint64_t *launches, double *ms, uint64_t *points) {
-  if (!ctx || kind > 7) return KH_E_ARG;
+  if (!ctx || kind > 8) return KH_E_ARG;
   if (launches) *launches = ctx->tm[kind].launches;
   if (ms) *ms = ctx->tm[kind].ms;
   if (points) *points = ctx->tm[kind].points;

@@ -1,12 +1,14 @@
 // kh_ctx.h -- the context behind include/kh_gpu.h and the helpers its translation units share:
 // kh_capi.cpp (open/close, targets, kh_scan, target files), kh_capi_bsgs.cpp, kh_capi_minikeys.cpp,
-// kh_capi_taproot.cpp and kh_capi_hooks.cpp.
+// kh_capi_taproot.cpp, kh_capi_kangaroo.cpp and kh_capi_hooks.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <stdio.h>
+#include <array>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -28,6 +30,40 @@ struct timing {
     ms += t;
     points += pts;
   }
+};
+
+// ==============================================================================================
+// kangaroo search (kh_capi_kangaroo.cpp): empty until kh_kang_setup, emptied by kh_release_walk
+// ==============================================================================================
+struct kang_state {
+  bool ready = false;     // kh_kang_setup succeeded
+  bool found = false;     // the key is known (at setup when Q = a*G, else by a resolved collision)
+  bool no_walk = false;   // Q = a*G: Q' is the point at infinity, nothing is ever launched
+  u256 a{}, W{}, key{};
+  ge Q{}, Qp{};           // the target and Q' = Q - a*G
+  bool dp_auto = false;
+  uint32_t dp_bits = 0;
+  u256 jd[KH_KANG_JUMPS]{};  // the jump distances
+  uint32_t N = 0;         // herd size
+  uint64_t seed = 0;
+  std::vector<uint32_t> gen;  // per kangaroo: how often it was placed afresh
+  uint32_t steps_per_launch = 0;  // 0 = automatic (kh_capi_kangaroo.cpp launch_steps)
+  uint32_t epoch = 0;             // of the last kh_kang_step / solve launch group (kang_args.epoch)
+  kh_kang_stats stats{};
+  struct entry {
+    u256 dist;
+    uint32_t index, kind;
+  };
+  struct xhash {
+    size_t operator()(const std::array<uint64_t, 4> &x) const { return (size_t)(x[0] ^ (x[1] * 0x9E3779B97F4A7C15ULL)); }
+  };
+  std::unordered_map<std::array<uint64_t, 4>, entry, xhash> table;  // distinguished points by x
+  // the herd (SoA over N, kh_kernels.h kang_args), the jump table, the prefix products' pad, the records
+  dev_buf<uint32_t> d_x, d_y, d_dist, d_unplaced, d_jumps;
+  dev_buf<unsigned long long> d_count;
+  dev_buf<uint4> d_pad;
+  dev_buf<kang_rec> d_recs;
+  std::vector<kang_rec> h_recs;
 };
 
 // ==============================================================================================
@@ -156,9 +192,11 @@ struct kh_ctx {
   dev_buf<uint32_t> d_tap_x, d_tap_y;
   uint32_t tap_dev_hits = 0;
 
+  kang_state kang;
+
   // timing
   gpu_event ev_a, ev_b;
-  timing tm[8];  // kh_kernel_time kinds 0..7
+  timing tm[9];  // kh_kernel_time kinds 0..8
 
   // pipelined BSGS rounds: double-buffered hit buffers, pinned host mirrors, host scalar arrays
   dev_buf<uint32_t> d_cnt2[2];

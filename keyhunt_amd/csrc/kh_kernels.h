@@ -180,6 +180,9 @@ struct setup_args {
   const uint32_t *list, *start;  // 8 LE u32 limbs per base, < n
   uint64_t t_round, lane_pts, a_pts, two_n, m;
   uint32_t h;
+  // with q, or null: bad[g] = 1 for a lane whose s_g*G is +-Q (the dx = 0 case below); a lane scalar of 0
+  // then stands for the point at infinity and its centre is Q itself (the kangaroo herds' placement)
+  uint32_t *bad;
 };
 
 // BSGS second check on the GPU (bsgs_secondcheck, keyhunt.cpp:5151-5184).  Per first-level
@@ -262,7 +265,63 @@ struct tap_keys_args {
                             // skipped point's 8 words are left as they were
 };
 
+// Pollard's lambda walk (-m kangaroo, k_kang_step).  The herd lives on the device as SoA: word w of kangaroo
+// e at [w*N + e], for the affine point (x, y) and the travelled distance (a plain 256-bit integer).  Lane g
+// of T owns the KH_KANG_BATCH kangaroos e = t*T + g, t < KH_KANG_BATCH, which share one inversion per step.
+// One jump: j = x mod 32, P += J[j], dist += d[j]; the new point is distinguished when the top dp_bits bits
+// of x are zero, and a distinguished point appends a kang_rec through the counting head dp_count.
+#define KH_KANG_JUMPS 32
+// Batch 32, streamed, 4 waves/SIMD: the fastest of nine forms once the herd fills the chip, 12.4 G jumps/s at
+// 2^23 kangaroos against 9.9 for batch 16 and 7.0 for batch 8 (profiles/kangaroo_rate_ab.json)
+#ifndef KH_KANG_BATCH
+#define KH_KANG_BATCH 32
+#endif
+#ifndef KH_KANG_LB
+#define KH_KANG_LB 4
+#endif
+#ifndef KH_KANG_STEPS
+#define KH_KANG_STEPS 256  // jumps per kangaroo per launch
+#endif
+#define KH_DKANG_STALL 0x10u  // the ABI's KH_KANG_STALL
+#define KH_KANG_TAB_WORDS 20  // per jump: x[8], y[8], d[4] (d < 2^128)
+struct kang_rec {
+  uint32_t x[8], dist[8];  // LE u32 limbs
+  uint32_t index, kind;    // kind: index & 1 (0 tame, 1 wild), | KH_DKANG_STALL
+};
+struct kang_args {
+  uint32_t *x, *y, *dist;    // 8 words each per kangaroo, SoA over N
+  uint32_t *flags;           // per kangaroo: bit 0 = its point could not be formed (dist*G = +-Q'), stalled for
+                             // good; bits 1..31 = the epoch of the call that last reported it stalled
+  uint32_t epoch;            // this call's, 1 .. 2^31 - 2: one stall report per kangaroo and call
+  uint32_t N;
+  uint32_t steps;            // jumps per kangaroo in this launch
+  uint32_t dp_bits;          // 0..32
+  const uint32_t *jumps;     // word-major: word w (< KH_KANG_TAB_WORDS) of jump j at [w*32 + j]
+  uint4 *pad;                // the prefix products: KH_KANG_BATCH rows x T lanes x 2
+  unsigned long long *dp_count;  // counts every record, also those past dp_cap
+  kang_rec *dps;
+  uint32_t dp_cap;
+};
+// k_kang_place: kangaroo e = first + i (or idx[i]), i < n, takes its point from the k_setup output of its
+// herd -- entry i/2 (or rank[i]) of the tame (even e) or wild (odd e) centres, SoA over n_tame / n_wild
+// lanes -- and its distance
+struct kang_place_args {
+  uint32_t *x, *y, *dist, *flags;
+  uint32_t N, first, n;
+  const uint32_t *idx, *rank;         // a list of kangaroos and each one's rank among those of its kind, or null
+  const uint32_t *tx, *ty, *wx, *wy;  // k_setup centres of the tames and the wilds among first .. first+n-1
+  uint32_t n_tame, n_wild;
+  const uint32_t *wbad;               // per wild: k_setup met dx = 0 (dist*G = +-Q')
+  const uint32_t *dists;              // n x 8 LE u32 limbs
+};
+
 namespace kh {
+// lanes (a multiple of 64) that walk a herd of N
+inline uint32_t kang_lanes(uint32_t N, uint32_t batch = KH_KANG_BATCH) {
+  return (uint32_t)(((uint64_t)N + 64ull * batch - 1) / (64ull * batch)) * 64u;
+}
+hipError_t launch_kang_step(const kang_args &A, hipStream_t st);
+hipError_t launch_kang_place(const kang_place_args &A, hipStream_t st);
 hipError_t launch_mini_filter(const mini_filter_args &A, hipStream_t st);
 hipError_t launch_mini_keys(const mini_keys_args &A, hipStream_t st);
 hipError_t launch_tap_keys(const tap_keys_args &A, hipStream_t st);

@@ -991,11 +991,17 @@ __global__ void __launch_bounds__(256) k_setup(setup_args A) {
     ge q;
     load_fe(q.x, A.q);
     load_fe(q.y, A.q + 8);
+    if (A.bad && acc.inf) {  // s = 0 (a kangaroo at distance 0): Q itself
+      store_soa(A.cx, A.L, g, q.x);
+      store_soa(A.cy, A.L, g, q.y);
+      return;
+    }
     fe z2, u2, h;  // h = Q.x*Z^2 - X: zero iff Q = +-s*G (AddDirect's dx = 0 case)
     fe_sqr(z2, acc.z);
     fe_mul(u2, q.x, z2);
     fe_sub(h, u2, acc.x);
     if (fe_is_zero(h)) {  // the affine AddDirect value, inverse of 0 taken as 0 (rare)
+      if (A.bad) A.bad[g] = 1;
       gej_to_ge(r, acc);
       ge_add(r, q, r);
       store_soa(A.cx, A.L, g, r.x);
@@ -1371,6 +1377,154 @@ __global__ void __launch_bounds__(64, 4) k_tap_keys(tap_keys_args A) {
 }
 
 // ------------------------------------------------------------------------------------------
+// Pollard's lambda walk (-m kangaroo).  Lane g of T walks the KH_KANG_BATCH kangaroos e = t*T + g of its batch
+// through A.steps jumps P += J[x mod 32], dist += d[x mod 32].  The 32 jumps {x, y, d} sit in LDS word-major,
+// so the lanes of a wave, which index them divergently, read word w of 32 different entries from 32 different
+// banks.  Per step the batch shares one inversion: forward the prefix products of dx = J.x - x, one fe_inv,
+// backward the slope, x and y of each kangaroo (5 multiplications and 1 squaring per jump + fe_inv / batch).
+// x, y and dist stream through HBM (coalesced SoA) and the prefix products through the lane's pad rows; dx is
+// formed again in the backward pass instead of being kept.  A form that kept the batch in registers across
+// the steps of a launch spilled and ran at a third of this one (DESIGN.md 2 "Kangaroo").
+// A kangaroo whose dx is 0 sits on +-J[j]: it puts 1 into the product, stays where it is for the rest of
+// the launch and is reported with KH_DKANG_STALL, as is one whose point could not be placed.  A report leaves
+// the call's epoch in the kangaroo's flag word, so the later launches of one call do not report it again.
+// ------------------------------------------------------------------------------------------
+namespace {
+__device__ __forceinline__ void kang_record(const kang_args &A, const fe &x, const uint32_t dist[8], uint32_t e,
+                                            uint32_t kind) {
+  const unsigned long long slot = atomicAdd(A.dp_count, 1ull);
+  if (slot < A.dp_cap) {
+    kang_rec &r = A.dps[slot];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      r.x[i] = x.d[i];
+      r.dist[i] = dist[i];
+    }
+    r.index = e;
+    r.kind = kind;
+  }
+}
+__device__ __forceinline__ void kang_jump_fe(fe &r, const uint32_t *s_j, int w0, uint32_t j) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.d[i] = s_j[(w0 + i) * KH_KANG_JUMPS + j];
+}
+}  // namespace
+
+__global__ void __launch_bounds__(64, KH_KANG_LB) k_kang_step(kang_args A) {
+  constexpr int B = KH_KANG_BATCH;
+  static_assert(B >= 1 && B <= 32, "the stall mask holds one bit per slot");
+  __shared__ uint32_t s_j[KH_KANG_TAB_WORDS * KH_KANG_JUMPS];
+  for (uint32_t i = threadIdx.x; i < KH_KANG_TAB_WORDS * KH_KANG_JUMPS; i += blockDim.x) s_j[i] = A.jumps[i];
+  __syncthreads();
+  const uint32_t T = gridDim.x * blockDim.x;
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t N = A.N;
+  if (g >= N) return;  // slot 0 is the lane's lowest index: no kangaroo at all
+  uint32_t stall = 0;  // bit t: slot t does not move in this launch (no kangaroo, unplaced, or dx = 0 met)
+#pragma unroll 1
+  for (int t = 0; t < B; t++) {
+    const uint64_t e = (uint64_t)t * T + g;
+    if (e >= N) {
+      stall |= 1u << t;
+      continue;
+    }
+    const uint32_t f = A.flags[e];
+    if ((f & 1u) || (f >> 1) == A.epoch) {  // no point, or a stall this call has already reported
+      stall |= 1u << t;
+      if ((f >> 1) == A.epoch) continue;
+      A.flags[e] = (f & 1u) | (A.epoch << 1);
+      fe x;
+      uint32_t dist[8];
+      load_soa(x, A.x, N, (uint32_t)e);
+#pragma unroll
+      for (int i = 0; i < 8; i++) dist[i] = A.dist[(size_t)i * N + e];
+      kang_record(A, x, dist, (uint32_t)e, ((uint32_t)e & 1u) | KH_DKANG_STALL);
+    }
+  }
+#pragma unroll 1
+  for (uint32_t step = 0; step < A.steps; step++) {
+    fe acc;
+    fe_set_u32(acc, 1);
+    // forward: prefix products of dx over the slots that move
+#pragma unroll 1
+    for (int t = 0; t < B; t++) {
+      scr_store(A.pad, (size_t)t * T + g, acc, g, T);
+      if ((stall >> t) & 1u) continue;
+      const uint32_t e = (uint32_t)t * T + g;
+      fe x, jx, dx;
+      load_soa(x, A.x, N, e);
+      kang_jump_fe(jx, s_j, 0, x.d[0] & (KH_KANG_JUMPS - 1));
+      fe_sub(dx, jx, x);
+      if (fe_is_zero(dx)) {  // on +-J[j]: reported once, unmoved from here on
+        stall |= 1u << t;
+        A.flags[e] = A.epoch << 1;
+        uint32_t dist[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) dist[i] = A.dist[(size_t)i * N + e];
+        kang_record(A, x, dist, e, (e & 1u) | KH_DKANG_STALL);
+        continue;
+      }
+      fe_mul(acc, acc, dx);
+    }
+    fe inv;
+    fe_inv(inv, acc);
+    // backward: 1/dx of each slot, the chord through P and J[j], the new point and distance
+#pragma unroll 1
+    for (int t = B - 1; t >= 0; t--) {
+      if ((stall >> t) & 1u) continue;
+      const uint32_t e = (uint32_t)t * T + g;
+      fe x, y, pre, jx, jy, dx, li, s, s2, x3, y3;
+      load_soa(x, A.x, N, e);
+      load_soa(y, A.y, N, e);
+      scr_load(pre, A.pad, (size_t)t * T + g, g, T);
+      const uint32_t j = x.d[0] & (KH_KANG_JUMPS - 1);
+      kang_jump_fe(jx, s_j, 0, j);
+      kang_jump_fe(jy, s_j, 8, j);
+      fe_sub(dx, jx, x);
+      fe_mul(li, inv, pre);
+      fe_mul(inv, inv, dx);
+      fe_sub(s, jy, y);
+      fe_mul(s, s, li);
+      fe_sqr(s2, s);
+      fe_sub(x3, s2, x);
+      fe_sub(x3, x3, jx);
+      fe_sub(y3, x, x3);
+      fe_mul(y3, y3, s);
+      fe_sub(y3, y3, y);
+      store_soa(A.x, N, e, x3);
+      store_soa(A.y, N, e, y3);
+      uint32_t dist[8], c = 0;
+#pragma unroll
+      for (int i = 0; i < 8; i++) {
+        const uint32_t dj = i < 4 ? s_j[(16 + i) * KH_KANG_JUMPS + j] : 0u;
+        dist[i] = addc(A.dist[(size_t)i * N + e], dj, c, c);
+        A.dist[(size_t)i * N + e] = dist[i];
+      }
+      // distinguished: the top dp_bits bits of x are zero (x is canonical)
+      if (A.dp_bits == 0 || (x3.d[7] >> (32 - A.dp_bits)) == 0) kang_record(A, x3, dist, e, e & 1u);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) k_kang_place(kang_place_args A) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.n) return;
+  // the tames and the wilds were set up in the order they come here, each herd on lanes of its own
+  const uint32_t e = A.idx ? A.idx[i] : A.first + i;
+  const uint32_t r = A.rank ? A.rank[i] : i >> 1;
+  const bool wild = e & 1u;
+  const uint32_t *sx = wild ? A.wx : A.tx, *sy = wild ? A.wy : A.ty;
+  const uint32_t L = wild ? A.n_wild : A.n_tame;
+#pragma unroll
+  for (int w = 0; w < 8; w++) {
+    A.x[(size_t)w * A.N + e] = sx[(size_t)w * L + r];
+    A.y[(size_t)w * A.N + e] = sy[(size_t)w * L + r];
+    A.dist[(size_t)w * A.N + e] = A.dists[(size_t)i * 8 + w];
+  }
+  A.flags[e] = wild ? A.wbad[r] : 0u;
+}
+
+// ------------------------------------------------------------------------------------------
 // Parity-test kernels (exercised by tests/ through the C-ABI): hash160 and bloom probes of
 // given inputs, field ops.
 // ------------------------------------------------------------------------------------------
@@ -1669,6 +1823,17 @@ hipError_t launch_mini_keys(const mini_keys_args &A, hipStream_t st) {
 hipError_t launch_tap_keys(const tap_keys_args &A, hipStream_t st) {
   const uint32_t lanes = (A.n + KH_TAP_BATCH - 1) / KH_TAP_BATCH;
   hipLaunchKernelGGL(k_tap_keys, dim3((lanes + 63) / 64), dim3(64), 0, st, A);
+  return hipGetLastError();
+}
+
+hipError_t launch_kang_step(const kang_args &A, hipStream_t st) {
+  if (!A.N) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_kang_step, dim3(kang_lanes(A.N) / 64), dim3(64), 0, st, A);
+  return hipGetLastError();
+}
+
+hipError_t launch_kang_place(const kang_place_args &A, hipStream_t st) {
+  hipLaunchKernelGGL(k_kang_place, dim3((A.n + 255) / 256), dim3(256), 0, st, A);
   return hipGetLastError();
 }
 

@@ -64,6 +64,20 @@ class KhMinikeyHit(ctypes.Structure):
                 ("minikey", ctypes.c_char * 24)]
 
 
+class KhKangDp(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_uint8 * 32), ("dist", ctypes.c_uint8 * 32), ("index", ctypes.c_uint32),
+                ("kind", ctypes.c_uint32)]
+
+
+class KhKangStats(ctypes.Structure):
+    _fields_ = [("jumps", ctypes.c_uint64), ("dps", ctypes.c_uint64), ("same_herd", ctypes.c_uint64),
+                ("reseeds", ctypes.c_uint64), ("stalls", ctypes.c_uint64), ("lost", ctypes.c_uint64),
+                ("bad", ctypes.c_uint64)]
+
+
+KH_KANG_TAME, KH_KANG_WILD, KH_KANG_STALL = 0, 1, 0x10
+KH_KANG_DP_AUTO = 0xFFFFFFFF
+TIME_KANG = 8
 MINIKEY_ALPHABET = "123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz"
 TIME_MINI_FILTER, TIME_MINI_KEYS = 5, 6
 TIME_TAP_KEYS = 7
@@ -162,6 +176,18 @@ def lib() -> ctypes.CDLL:
     L.kh_taproot_set_window.argtypes = [P, ctypes.c_uint64]
     L.kh_taproot_outputs.argtypes = [P, u8p, ctypes.c_uint32, u8p]
     L.kh_taproot_stats.argtypes = [P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    L.kh_kang_setup.argtypes = [P, u8p, u8p, u8p, ctypes.c_uint32, u8p]
+    L.kh_kang_jumps.argtypes = [P, u8p]
+    L.kh_kang_geometry.argtypes = [P, u32p, u32p, u32p, u32p]
+    L.kh_kang_set_launch.argtypes = [P, ctypes.c_uint32]
+    L.kh_kang_set_herd.argtypes = [P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u8p]
+    L.kh_kang_seed.argtypes = [P, ctypes.c_uint64, ctypes.c_uint32]
+    L.kh_kang_step.argtypes = [P, ctypes.c_uint32, ctypes.POINTER(KhKangDp), ctypes.c_uint32, u32p, u64p]
+    L.kh_kang_get_herd.argtypes = [P, ctypes.c_uint32, ctypes.c_uint32, u8p, u8p]
+    L.kh_kang_add_dps.argtypes = [P, ctypes.POINTER(KhKangDp), ctypes.c_uint32, u8p, u32p]
+    L.kh_kang_resolve.argtypes = [u8p, u8p, u8p, u8p, u8p]
+    L.kh_kang_solve.argtypes = [P, ctypes.c_uint64, u8p, u32p, ctypes.POINTER(KhKangStats)]
     _lib = L
     return L
 
@@ -174,6 +200,15 @@ def device_count() -> int:
 
 def be32(v: int) -> bytes:
     return (int(v) % (1 << 256)).to_bytes(32, "big")
+
+
+def kang_resolve(tame_dist: int, wild_dist: int, start: int, pub: tuple[int, int]) -> int | None:
+    """kh_kang_resolve (host only, no context): the key of a tame/wild collision, or None."""
+    key = ctypes.create_string_buffer(32)
+    r = lib().kh_kang_resolve(be32(tame_dist), be32(wild_dist), be32(start), be32(pub[0]) + be32(pub[1]), key)
+    if r < 0:
+        raise KhError(f"kh_kang_resolve: {lib().kh_strerror(r).decode()}")
+    return int.from_bytes(key.raw, "big") if r else None
 
 
 @dataclass
@@ -392,6 +427,83 @@ class Engine:
         a, b = ctypes.c_uint32(), ctypes.c_uint32()
         self._chk(lib().kh_taproot_stats(self._ctx, ctypes.byref(a), ctypes.byref(b)), "kh_taproot_stats")
         return a.value, b.value
+
+    # -- kangaroo ------------------------------------------------------------------------------
+    # distinguished points travel as (x, dist, index, kind) tuples of integers
+    def kang_setup_status(self, pub: tuple[int, int], start: int, end: int, dp_bits: int = KH_KANG_DP_AUTO,
+                          jumps: list[int] = None) -> int:
+        jb = b"".join(be32(d) for d in jumps) if jumps is not None else None
+        return lib().kh_kang_setup(self._ctx, be32(pub[0]) + be32(pub[1]), be32(start), be32(end), dp_bits, jb)
+
+    def kang_setup(self, pub: tuple[int, int], start: int, end: int, dp_bits: int = KH_KANG_DP_AUTO,
+                   jumps: list[int] = None) -> int:
+        """Target `pub` with its key in [start, end]; returns KH_KANG_BATCH, the kangaroos per lane."""
+        self._chk(self.kang_setup_status(pub, start, end, dp_bits, jumps), "kh_kang_setup")
+        return self.kang_geometry()[0]
+
+    def kang_jumps(self) -> list[int]:
+        out = ctypes.create_string_buffer(32 * 32)
+        self._chk(lib().kh_kang_jumps(self._ctx, out), "kh_kang_jumps")
+        return [int.from_bytes(out.raw[32 * j:32 * j + 32], "big") for j in range(32)]
+
+    def kang_geometry(self) -> tuple[int, int, int, int]:
+        """(batch, jumps per kangaroo per launch, herd size, dp_bits)."""
+        v = [ctypes.c_uint32() for _ in range(4)]
+        self._chk(lib().kh_kang_geometry(self._ctx, *[ctypes.byref(x) for x in v]), "kh_kang_geometry")
+        return tuple(x.value for x in v)
+
+    def kang_set_launch(self, steps_per_launch: int = 0) -> None:
+        self._chk(lib().kh_kang_set_launch(self._ctx, steps_per_launch), "kh_kang_set_launch")
+
+    def kang_set_herd_status(self, total: int, first: int, dists: list[int]) -> int:
+        return lib().kh_kang_set_herd(self._ctx, total, first, len(dists), b"".join(be32(d) for d in dists))
+
+    def kang_set_herd(self, total: int, first: int, dists: list[int]) -> None:
+        self._chk(self.kang_set_herd_status(total, first, dists), "kh_kang_set_herd")
+
+    def kang_seed(self, seed: int, n_kangaroos: int = 0) -> int:
+        """Place the whole herd by the library's rule; returns the herd's size."""
+        self._chk(lib().kh_kang_seed(self._ctx, seed, n_kangaroos), "kh_kang_seed")
+        return self.kang_geometry()[2]
+
+    @staticmethod
+    def _dp_tuple(d: KhKangDp) -> tuple[int, int, int, int]:
+        return int.from_bytes(bytes(d.x), "big"), int.from_bytes(bytes(d.dist), "big"), d.index, d.kind
+
+    def kang_step_raw(self, steps: int, buf, cap: int) -> tuple[int, int]:
+        """kh_kang_step into a caller's KhKangDp array; (records written, records lost)."""
+        n, lost = ctypes.c_uint32(), ctypes.c_uint64()
+        self._chk(lib().kh_kang_step(self._ctx, steps, buf, cap, ctypes.byref(n), ctypes.byref(lost)), "kh_kang_step")
+        return n.value, lost.value
+
+    def kang_step(self, steps: int, cap: int) -> tuple[list[tuple[int, int, int, int]], int]:
+        buf = (KhKangDp * max(1, cap))()
+        n, lost = self.kang_step_raw(steps, buf, cap)
+        return [self._dp_tuple(buf[i]) for i in range(n)], lost
+
+    def kang_get_herd(self, first: int, n: int) -> list[tuple[int, int, int]]:
+        """(x, y, dist) of kangaroos first .. first+n-1."""
+        xy, dist = ctypes.create_string_buffer(64 * n), ctypes.create_string_buffer(32 * n)
+        self._chk(lib().kh_kang_get_herd(self._ctx, first, n, xy, dist), "kh_kang_get_herd")
+        f = int.from_bytes
+        return [(f(xy.raw[64 * i:64 * i + 32], "big"), f(xy.raw[64 * i + 32:64 * i + 64], "big"),
+                 f(dist.raw[32 * i:32 * i + 32], "big")) for i in range(n)]
+
+    def kang_add_dps(self, dps: list[tuple[int, int, int, int]]) -> int | None:
+        """Feed records to the context's table; the key once it is known, else None."""
+        buf = (KhKangDp * max(1, len(dps)))()
+        for i, (x, dist, index, kind) in enumerate(dps):
+            buf[i].x[:] = be32(x)
+            buf[i].dist[:] = be32(dist)
+            buf[i].index, buf[i].kind = index, kind
+        key, found = ctypes.create_string_buffer(32), ctypes.c_uint32()
+        self._chk(lib().kh_kang_add_dps(self._ctx, buf, len(dps), key, ctypes.byref(found)), "kh_kang_add_dps")
+        return int.from_bytes(key.raw, "big") if found.value else None
+
+    def kang_solve(self, max_jumps: int) -> tuple[int | None, KhKangStats]:
+        key, found, st = ctypes.create_string_buffer(32), ctypes.c_uint32(), KhKangStats()
+        self._chk(lib().kh_kang_solve(self._ctx, max_jumps, key, ctypes.byref(found), ctypes.byref(st)), "kh_kang_solve")
+        return (int.from_bytes(key.raw, "big") if found.value else None), st
 
     # -- BSGS ----------------------------------------------------------------------------------
     def bsgs_setup(self, n: int, k: int, layer1: int = None) -> KhBsgsInfo:

@@ -12,6 +12,8 @@
 // cache, in the reference's formats) and -B ggsb / --bsgs-block-count / --bsgs-block-size are
 // provided.  Built with -DKH_WITH_MINIKEYS (bin/minikeys-amd) the same source also takes -m minikeys
 // with -C and -8 (thread_process_minikeys, keyhunt.cpp:3094-3259); bin/keyhunt-amd rejects that mode.
+// -m kangaroo is the engine's own mode (the reference has none): Pollard's lambda search for the public keys
+// of FILE in a bounded range, with --dp, --herd and --seed (run_kangaroo).
 #include <getopt.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -23,6 +25,7 @@
 #include <algorithm>
 #include <random>
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <mutex>
 #include <string>
@@ -47,7 +50,7 @@ const char *VERSION = "keyhunt-amd 0.1 (MI355X engine for keyhunt 0.2.230519 hot
 // options and shared state
 // ---------------------------------------------------------------------------------------------
 // MODE_MINIKEYS is a mode name of the build with KH_WITH_MINIKEYS only (bin/minikeys-amd)
-enum { MODE_ADDRESS, MODE_RMD160, MODE_XPOINT, MODE_BSGS, MODE_VANITY, MODE_MINIKEYS };
+enum { MODE_ADDRESS, MODE_RMD160, MODE_XPOINT, MODE_BSGS, MODE_VANITY, MODE_KANGAROO, MODE_MINIKEYS };
 struct options {
   int mode = MODE_ADDRESS;
   const char *file = nullptr;
@@ -97,6 +100,12 @@ struct options {
   // --taproot (-m address; the reference has no such option): bc1p... lines are targets, searched by
   // kh_taproot_scan after each chunk's kh_scan.  Key-path-only outputs (BIP-86, no script tree) only.
   bool taproot = false;
+  // -m kangaroo: --dp BITS (default: the library's), --herd N (0: the library's), --seed U64 (default: from the
+  // OS); and which of the options the mode refuses were given
+  uint32_t kang_dp = KH_KANG_DP_AUTO, kang_herd = 0;
+  uint64_t kang_seed = 0;
+  bool kang_seed_given = false;
+  bool k_given = false, l_given = false, B_given = false, mapped_given = false, ptable_given = false;
 } opt;
 // --segwit: what the target reader saw -- bech32 P2WPKH rows, base58 lines of version byte 05
 uint64_t g_seg_bech32 = 0, g_seg_p2sh = 0;
@@ -1325,6 +1334,9 @@ void usage(const char *p) {
 #ifdef KH_WITH_MINIKEYS
          "       -m minikeys -f FILE [-C MINIKEY] [-8 ALPHABET] [-n N] [-R]\n"
 #endif
+         "       -m kangaroo -f FILE (-r START:END | -b BITS) [--dp BITS] [--herd N] [--seed U64] [-q]\n"
+         "       Pollard's lambda search for the public keys of FILE (as -m bsgs reads it), one after another, in a\n"
+         "       range of width 2^16 .. 2^192: about 2*sqrt(width) jumps whatever the width.  One GPU.\n"
          , p);
 }
 
@@ -1340,7 +1352,7 @@ const U ORDER = [] {
 // The command line into opt and mapped::cfg, with the lines the reference prints as it reads each
 // option.  False when the program ends here, with `status`.
 bool parse_options(int argc, char **argv, int &status) {
-  const char *mode_names[] = {"address", "rmd160", "xpoint", "bsgs", "vanity", "minikeys"};
+  const char *mode_names[] = {"address", "rmd160", "xpoint", "bsgs", "vanity", "kangaroo", "minikeys"};
   static const struct option long_opts[] = {{"bsgs-block-count", required_argument, 0, 1},
                                            {"bsgs-block-size", required_argument, 0, 2},
                                            {"ptable", required_argument, 0, 3},
@@ -1358,6 +1370,9 @@ bool parse_options(int argc, char **argv, int &status) {
                                            {"rmd-batch-size", required_argument, 0, 15},
                                            {"segwit", no_argument, 0, 16},
                                            {"taproot", no_argument, 0, 17},
+                                           {"dp", required_argument, 0, 18},
+                                           {"herd", required_argument, 0, 19},
+                                           {"seed", required_argument, 0, 20},
                                            {0, 0, 0, 0}};
   // --mapped-size / --bloom-bytes / --create-mapped N: the entry count and error the byte budget
   // allows (bloom_entries_for_bytes, keyhunt.cpp:7510-7530)
@@ -1372,10 +1387,10 @@ bool parse_options(int argc, char **argv, int &status) {
   };
 #ifdef KH_WITH_MINIKEYS
   const char *short_opts = "m:f:l:r:b:k:n:t:g:qs:I:L:MRec:B:S6v:z:dhC:8:";
-  const int n_modes = 6;
+  const int n_modes = 7;
 #else
   const char *short_opts = "m:f:l:r:b:k:n:t:g:qs:I:L:MRec:B:S6v:z:dh";
-  const int n_modes = 5;
+  const int n_modes = 6;
 #endif
   int c;
   while ((c = getopt_long(argc, argv, short_opts, long_opts, nullptr)) != -1) {
@@ -1418,7 +1433,7 @@ bool parse_options(int argc, char **argv, int &status) {
         opt.ggsb = opt.ggsb_size > 0;
         break;
       case 3: opt.ptable = optarg; break;                    // keyhunt.cpp:772-773
-      case 4: opt.ptable_size = parse_size(optarg); break;   // keyhunt.cpp:774-785
+      case 4: opt.ptable_size = parse_size(optarg); opt.ptable_given = true; break;   // keyhunt.cpp:774-785
       case 5: opt.load_ptable = true; break;                 // keyhunt.cpp:786-787
       case 6: opt.ptable_cache = true; break;                // keyhunt.cpp:788-789
       case 7:                                                // keyhunt.cpp:744-748
@@ -1433,8 +1448,8 @@ bool parse_options(int argc, char **argv, int &status) {
         opt.mapped = true;
         mapped::cfg.chunks = (uint32_t)strtoul(optarg, NULL, 10);
         break;
-      case 10: mapped::cfg.name = optarg; break;      // keyhunt.cpp:768-769 (does not set --mapped)
-      case 11: mapped::cfg.load_bloom = true; break;  // keyhunt.cpp:770-771
+      case 10: mapped::cfg.name = optarg; opt.mapped_given = true; break;      // keyhunt.cpp:768-769 (does not set --mapped)
+      case 11: mapped::cfg.load_bloom = true; opt.mapped_given = true; break;  // keyhunt.cpp:770-771
       case 12:                                        // keyhunt.cpp:790-796
         opt.mapped = true;
         size_override(strtoull(optarg, NULL, 10));
@@ -1456,6 +1471,12 @@ bool parse_options(int argc, char **argv, int &status) {
         opt.rmd_batch = (int)v;
         break;
       }
+      case 18: opt.kang_dp = (uint32_t)strtoul(optarg, NULL, 10); break;   // checked in check_kangaroo
+      case 19: opt.kang_herd = (uint32_t)strtoul(optarg, NULL, 10); break;
+      case 20:
+        opt.kang_seed = strtoull(optarg, NULL, 0);
+        opt.kang_seed_given = true;
+        break;
       case 17: opt.taproot = true; break;  // -m address: bc1p... targets (checked in check_options)
       case 16: opt.segwit = true; break;  // -m address: bech32 and P2SH-P2WPKH targets (checked in check_options)
       case 'm': {
@@ -1483,6 +1504,7 @@ bool parse_options(int argc, char **argv, int &status) {
         break;
       case 'l':
         // keyhunt.cpp:945-960
+        opt.l_given = true;
         if (!strcmp(optarg, "compress")) { opt.search = KH_SEARCH_COMPRESS; printf("[+] Search compress only\n"); }
         else if (!strcmp(optarg, "uncompress")) { opt.search = KH_SEARCH_UNCOMPRESS; printf("[+] Search uncompress only\n"); }
         else if (!strcmp(optarg, "both")) { opt.search = KH_SEARCH_BOTH; printf("[+] Search both compress and uncompress\n"); }
@@ -1512,7 +1534,7 @@ bool parse_options(int argc, char **argv, int &status) {
           fprintf(stderr, "[E] invalid bits param: %s.\n", optarg);
         }
         break;
-      case 'k': opt.kfactor = strtoull(optarg, nullptr, 10); if (!opt.kfactor) opt.kfactor = 1; printf("[+] K factor %llu\n", (unsigned long long)opt.kfactor); break;
+      case 'k': opt.k_given = true; opt.kfactor = strtoull(optarg, nullptr, 10); if (!opt.kfactor) opt.kfactor = 1; printf("[+] K factor %llu\n", (unsigned long long)opt.kfactor); break;
       case 'n': opt.flag_n = true; opt.n = parse_n(optarg); break;
       case 't': {  // host threads: one per GPU context here (see -g); echoed as keyhunt.cpp:1076-1082 does
         long t = strtol(optarg, NULL, 10);
@@ -1550,6 +1572,7 @@ bool parse_options(int argc, char **argv, int &status) {
         opt.bsgs_mode = BM_RANDOM;
         break;
       case 'B': {  // keyhunt.cpp:841-853
+        opt.B_given = true;
         int idx = -1;
         for (int i = 0; i < 7; i++)
           if (!strcmp(optarg, BSGS_MODES[i])) idx = i;
@@ -1602,8 +1625,37 @@ bool parse_options(int argc, char **argv, int &status) {
     fprintf(stderr, "--load-ptable requires --ptable <file>\n");
     return fail();
   }
-  if (opt.create_mapped) {  // keyhunt.cpp:1131-1172: make the file(s) from the whole command line and exit
+  if (opt.create_mapped && opt.mode != MODE_KANGAROO) {  // keyhunt.cpp:1131-1172: make the file(s) from the whole command line and exit
     status = mapped::create();
+    return false;
+  }
+  return true;
+}
+
+// -m kangaroo takes -f, -r / -b, -g 1, -q, -s, -t and its own --dp, --herd, --seed; every option that shapes
+// another mode's search is refused, one line each, before any GPU is opened
+bool check_kangaroo() {
+  const char *why = opt.endo                                                  ? "-e (endomorphism) doesn't work with -m kangaroo"
+                    : opt.stride_set                                          ? "-I (stride) doesn't work with -m kangaroo"
+                    : opt.B_given                                             ? "-B (BSGS schedule) doesn't work with -m kangaroo"
+                    : opt.k_given                                             ? "-k (BSGS k factor) doesn't work with -m kangaroo"
+                    : opt.flag_n                                              ? "-n doesn't work with -m kangaroo"
+                    : opt.save_read                                           ? "-S doesn't work with -m kangaroo (there are no tables to save)"
+                    : opt.crypto_given                                        ? "-c doesn't work with -m kangaroo (the targets are public keys)"
+                    : opt.l_given                                             ? "-l doesn't work with -m kangaroo (the targets are public keys)"
+                    : opt.segwit                                              ? "--segwit doesn't work with -m kangaroo"
+                    : opt.taproot                                             ? "--taproot doesn't work with -m kangaroo"
+                    : (opt.mapped || opt.create_mapped || opt.mapped_given)   ? "the mapped bloom options don't work with -m kangaroo"
+                    : (opt.ptable || opt.load_ptable || opt.ptable_cache || opt.ptable_given)
+                        ? "the ptable options don't work with -m kangaroo"
+                    : opt.gpus > 1                                            ? "-m kangaroo runs on one GPU (-g 1)"
+                    : (opt.kang_dp > 32 && opt.kang_dp != KH_KANG_DP_AUTO)    ? "--dp takes 0 .. 32"
+                    : opt.kang_herd > (1u << 24)                              ? "--herd takes at most 16777216"
+                    : (!opt.have_bits && !opt.have_range)
+                        ? "-m kangaroo needs a bounded range: -r START:END or -b BITS"
+                        : nullptr;
+  if (why) {
+    fprintf(stderr, "[E] %s\n", why);
     return false;
   }
   return true;
@@ -1615,6 +1667,7 @@ bool check_options() {
     fprintf(stderr, "[E] -f FILE is required\n");
     return false;
   }
+  if (opt.mode == MODE_KANGAROO) return check_kangaroo();
   if (!validate_nk(opt.n, opt.kfactor)) return false;  // keyhunt.cpp:1173-1183: applied to every mode
   // keyhunt.cpp:1185-1193 compares the -B index with MODE_BSGS (2), i.e. these two guards fire
   // for -B both whatever -m is (SURVEY 8a parity note 7); BSGS itself ignores -e and -I
@@ -2000,6 +2053,98 @@ int run_bsgs(run &R) {
   return 0;
 }
 
+// -m kangaroo: the range as the inclusive interval [a, b] the library takes (-b BITS: 2^(BITS-1) .. 2^BITS - 1; -r
+// A:B as typed; an end at the group order stops one below it), or false with the message when its width
+// is outside the method's limits
+bool kangaroo_range(U &a, U &b) {
+  if (!opt.have_bits && !opt.have_range) {  // setup_range refused -r's values
+    fprintf(stderr, "[E] -m kangaroo needs a bounded range: -r START:END or -b BITS\n");
+    return false;
+  }
+  a = opt.start;
+  b = opt.have_bits || u_cmp(opt.end, ORDER) >= 0 ? u_sub(opt.end, u_from_u64(1)) : opt.end;
+  const int wl = u_cmp(b, a) > 0 ? u_bitlen(u_sub(b, a)) : 0;
+  if (wl <= 16 || wl > 192) {
+    fprintf(stderr, "[E] -m kangaroo needs a range at least 2^16 and less than 2^192 keys wide\n");
+    return false;
+  }
+  return true;
+}
+
+// -m kangaroo: the targets as -m bsgs reads them, then one kh_kang_solve loop per target, in file order, on
+// one context.  A found key is printed and recorded as the sequential BSGS worker's.  The exit status.
+int run_kangaroo(run &R, const U &a, const U &b) {
+  if (int rc = read_bsgs_targets(R)) return rc;
+  print_range();
+  if (!open_devices(R)) return EXIT_FAILURE;
+  kh_ctx *ctx = nullptr;
+  int r = kh_open(0, &ctx);
+  if (r) {
+    fprintf(stderr, "[E] kh_open: %s\n", kh_strerror(r));
+    return EXIT_FAILURE;
+  }
+  const uint64_t seed = opt.kang_seed_given ? opt.kang_seed : ((uint64_t)std::random_device{}() << 32) | std::random_device{}();
+  uint8_t ab[32], bb[32];
+  u_to_be32(a, ab);
+  u_to_be32(b, bb);
+  long double sqrt_w = 0;
+  {
+    const U w = u_sub(b, a);
+    for (int i = 3; i >= 0; i--) sqrt_w = sqrt_w * 18446744073709551616.0L + (long double)w.v[i];
+    sqrt_w = sqrtl(sqrt_w);
+  }
+  printf("[+] Kangaroo seed %llu\n", (unsigned long long)seed);
+  int rc = EXIT_SUCCESS;
+  for (size_t t = 0; t < R.tx.size() && rc == EXIT_SUCCESS; t++) {
+    uint8_t pub[64], key[32];
+    fe_to_be(pub, R.tx[t]);
+    fe_to_be(pub + 32, R.ty[t]);
+    if (!r) r = kh_kang_setup(ctx, pub, ab, bb, opt.kang_dp, nullptr);
+    if (!r) r = kh_kang_seed(ctx, seed, opt.kang_herd);
+    uint32_t herd = 0, dp = 0, spl = 0, found = 0;
+    if (!r) r = kh_kang_geometry(ctx, nullptr, &spl, &herd, &dp);
+    if (!r && herd) printf("[+] Kangaroo target %zu: herd %u, dp %u\n", t + 1, herd, dp);
+    // calls of about a second: one launch first, then as many jumps as the measured rate does in that time
+    uint64_t per_call = (uint64_t)herd * spl;
+    kh_kang_stats st{};
+    const auto t0 = std::chrono::steady_clock::now();
+    while (!r && !found) {
+      const auto c0 = std::chrono::steady_clock::now();
+      const uint64_t before = st.jumps;
+      r = kh_kang_solve(ctx, per_call, key, &found, &st);
+      const auto c1 = std::chrono::steady_clock::now();
+      const double dt = std::chrono::duration<double>(c1 - c0).count(), all = std::chrono::duration<double>(c1 - t0).count();
+      if (dt > 0 && st.jumps > before) per_call = std::max<uint64_t>((uint64_t)herd * spl, (uint64_t)((st.jumps - before) / dt));
+      if (!opt.quiet && !r) {
+        printf("\r[+] Kangaroo: %.3e jumps, %.3e jumps/s, %llu DPs, %.2Lf x sqrt(W)   %s", (double)st.jumps,
+               all > 0 ? st.jumps / all : 0.0, (unsigned long long)st.dps, sqrt_w > 0 ? st.jumps / sqrt_w : 0.0L,
+               found ? "\n" : "\r");
+        fflush(stdout);
+      }
+    }
+    if (r) {
+      fprintf(stderr, "[E] kangaroo: %s (%s)\n", kh_strerror(r), kh_last_error(ctx));
+      rc = EXIT_FAILURE;
+      break;
+    }
+    const std::string k = u_hex(u_from_be32(key));
+    uint8_t pxy[64];
+    kh_pubkeys(ctx, key, 1, pxy);
+    const std::string pubt = pubkey_text(pxy, R.comp[t]);
+    printf("[+] Thread Key found privkey %s   ", k.c_str());  // the sequential BSGS worker's lines (print_found)
+    printf("[+] Publickey %s\n", pubt.c_str());
+    FILE *f = fopen("KEYFOUNDKEYFOUND.txt", "a");
+    if (f) {
+      fprintf(f, "Key found privkey %s\nPublickey %s\n", k.c_str(), pubt.c_str());
+      fclose(f);
+    }
+    fflush(stdout);
+  }
+  kh_close(ctx);
+  printf("\nEnd\n");
+  return rc;
+}
+
 // the stats loop (keyhunt.cpp:2850-2962) until every worker has ended; the program's exit status
 int wait_for_workers(run &R) {
   uint64_t secs = 0;
@@ -2024,6 +2169,11 @@ int main(int argc, char **argv) {
   if (!check_options()) return EXIT_FAILURE;
   setup_range();
   run R;
+  if (opt.mode == MODE_KANGAROO) {
+    U a, b;
+    if (!kangaroo_range(a, b)) return EXIT_FAILURE;
+    return run_kangaroo(R, a, b);
+  }
   if (int rc = opt.mode == MODE_BSGS ? run_bsgs(R) : run_address_family(R)) return rc;
   return wait_for_workers(R);
 }
