@@ -283,9 +283,10 @@ int kh_kang_geometry(kh_ctx *ctx, uint32_t *batch, uint32_t *steps_per_launch, u
 /* jumps per kangaroo per launch for the following steps (0 = automatic, see kh_kang_geometry) */
 int kh_kang_set_launch(kh_ctx *ctx, uint32_t steps_per_launch);
 /* A herd of `total` kangaroos (1..2^24; a first call, or another total, resizes the herd and empties the table):
- * kangaroos first .. first+n-1 are placed at dists (n x 32 bytes) through the lane-setup kernel.  KH_E_ARG: a
- * tame distance of 0, first + n > total.  A wild with dist*G = +-Q' has no point: it is marked stalled and
- * the next step reports it. */
+ * kangaroos first .. first+n-1 are placed at dists (n x 32 bytes) through the lane-setup kernel; a distance
+ * at or above the group order n is kept as given and its point formed from dist mod n.  KH_E_ARG, with the
+ * herd as it was: a tame distance that is 0 mod n (0 or n itself: no point), first + n > total.  A wild with
+ * dist*G = +-Q' has no point: it is marked stalled and the next step reports it. */
 int kh_kang_set_herd(kh_ctx *ctx, uint32_t total, uint32_t first, uint32_t n, const uint8_t *dists);
 /* The same with the library's distances for all n_kangaroos (0: the default herd, never more than sqrt(W)/128
  * rounded down to a power of two -- a sixteenth of the sqrt(W)/8 bound, so that the automatic dp_bits is 4 or

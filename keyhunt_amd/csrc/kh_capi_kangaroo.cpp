@@ -470,8 +470,8 @@ int kh_kang_set_herd(kh_ctx *ctx, uint32_t total, uint32_t first, uint32_t n, co
   std::vector<u256> d(n);
   for (uint32_t i = 0; i < n; i++) {
     d[i] = u256_from_be(dists + (size_t)i * 32);
-    if (!((first + i) & 1u) && u256_is_zero(d[i])) {
-      ctx->err = "kangaroo: a tame kangaroo at distance 0 has no point";
+    if (!((first + i) & 1u) && u256_is_zero(sc_reduce(d[i]))) {  // 0 or the group order: place() reduces mod n
+      ctx->err = "kangaroo: a tame kangaroo at a distance of 0 mod n has no point";
       return KH_E_ARG;
     }
   }

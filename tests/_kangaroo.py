@@ -77,6 +77,24 @@ def default_dp(n: int, W: int) -> int:
     return dp
 
 
+def launch_steps(n: int, W: int) -> int:
+    """Jumps per kangaroo per launch when none is set: the largest power of two up to 256 that keeps a launch
+    of the whole herd below sqrt(W)/16 jumps."""
+    s = 1
+    while s < 256 and n and isqrt_div8_fits(n * s * 4, W):
+        s *= 2
+    return s
+
+
+def default_herd(W: int) -> int:
+    """The herd kh_kang_seed places for n_kangaroos = 0: sqrt(W)/128 rounded down to a power of two, at least
+    64 and at most 2^23."""
+    n = 64
+    while n < (1 << 23) and isqrt_div8_fits(n * 32, W):
+        n *= 2
+    return n
+
+
 def is_dp(x: int, dp_bits: int) -> bool:
     return dp_bits == 0 or (x >> (256 - dp_bits)) == 0
 
@@ -98,6 +116,8 @@ class Herd:
         self.jd = list(jumps) if jumps is not None else default_jumps(self.W)
         self.J = [mul_g(d) for d in self.jd]
         self.k = []      # per kangaroo [point or None (it could not be placed), dist]
+        self.ids = None  # seed_some: the true index of each entry of k (None: entry e is kangaroo e)
+        self.on_jump = None  # called as on_jump(index, j, dist) for every jump taken, dist before the jump
         self.gen = []
         self.table = {}  # x -> (dist, index, kind)
         self.stats = dict(jumps=0, dps=0, same_herd=0, reseeds=0, stalls=0, bad=0)
@@ -120,11 +140,20 @@ class Herd:
             self.k[first + i] = [self.point_at(first + i, d), d]
 
     def seed_herd(self, seed: int, n: int):
-        self.seed = seed
+        self.seed, self.ids = seed, None
         self.k, self.gen = [], [0] * n
         self.table, self.key = {}, None
         self.stats = dict.fromkeys(self.stats, 0)
         self.set_herd(n, 0, [seed_dist(self.W, seed, i, 0) for i in range(n)])
+
+    def seed_some(self, seed: int, total: int, ids: list[int]):
+        """Only the kangaroos `ids` of a seeded herd of `total`, each under its true index: kangaroos do not
+        depend on each other, so their placement, walk and records are those of the whole herd's.  The table
+        (add_dps, solve) is not for such a herd."""
+        assert all(0 <= i < total for i in ids) and len(set(ids)) == len(ids)
+        self.seed_herd(seed, 0)
+        self.ids = list(ids)
+        self.k = [[self.point_at(i, d), d] for i in ids for d in [seed_dist(self.W, seed, i, 0)]]
 
     # -- the walk -----------------------------------------------------------------------------
     def step(self, steps: int, spl: int):
@@ -134,6 +163,7 @@ class Herd:
         three multiplications each), which changes no value: the dense tests walk 10^5 .. 10^6 jumps."""
         recs, stalled_seen = [], set()
         J, jd, k = self.J, self.jd, self.k
+        ix = self.ids if self.ids is not None else range(len(k))
         for lo in range(0, steps, spl):
             frozen = set()
             for _ in range(min(spl, steps - lo)):
@@ -146,7 +176,7 @@ class Herd:
                         frozen.add(e)
                         if e not in stalled_seen:
                             stalled_seen.add(e)
-                            recs.append((pt[0] if pt is not None else None, dist, e, (e & 1) | STALL))
+                            recs.append((pt[0] if pt is not None else None, dist, ix[e], (ix[e] & 1) | STALL))
                         continue
                     live.append(e)
                     dxs.append(dx)
@@ -161,16 +191,19 @@ class Herd:
                     j = x % JUMPS
                     li = inv * pre[i] % P
                     inv = inv * dxs[i] % P
+                    if self.on_jump is not None:
+                        self.on_jump(ix[e], j, dist)
                     s = (J[j][1] - y) * li % P
                     x3 = (s * s - x - J[j][0]) % P
                     k[e] = [(x3, (s * (x - x3) - y) % P), dist + jd[j]]
                     if is_dp(x3, self.dp_bits):
-                        recs.append((x3, dist + jd[j], e, e & 1))
+                        recs.append((x3, dist + jd[j], ix[e], ix[e] & 1))
         self.stats["jumps"] += len(k) * steps
         return recs
 
     # -- the table ----------------------------------------------------------------------------
     def add_dps(self, recs):
+        assert self.ids is None
         again = []
         for x, dist, index, kind in sorted(recs, key=lambda r: (r[2], r[1])):
             if self.key is not None:
